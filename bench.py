@@ -7,7 +7,7 @@ A step = serialization/plan + forward + backward (seeded random cotangent) of th
 PT-v3m1 (91.71 M params) on one "room-102400" chunk already resident in HBM; data loading and the
 optimizer are outside the metric.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -21,10 +21,6 @@ sys.path.insert(0, ROOT)
 # before torch is imported and long before any GPU call: the host driver only supports dmabuf IPC (RCCL / tensor sharing across
 # processes fails otherwise), and the HSA runtime reads the variable once, when it initialises
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# HIP maps streams onto 4 hardware queues by default.  With a process group initialised (RCCL's streams) the plan-building side
-# stream came to share a queue with the compute stream: its device->host round trips then waited for the whole step and the host
-# blocked 35 ms per step (one-rank rehearsal, round 3: 42.2 -> 39.5 ms/step with 8 queues).  Read once, when HIP initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 # The contract is ONE JSON line on stdout.  Native libraries write there too (RCCL prints a five-line version banner to stdout when
 # a process group comes up): file descriptor 1 is pointed at stderr for the whole run and the JSON line goes to the saved descriptor.
@@ -80,7 +76,44 @@ def parse():
                     "`sustained` {ms, socket_power_w, sclk_mhz} to its roofline object; off by default: thousands of extra launches would "
                     "dominate the per-kernel averages of a rocprofv3 trace of this command)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the config-3 and fp32-conv secondary lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (forward output and parameter gradients, "
+                         "fixed seeded samples of them) as DIR/<name>.npy in float32 / float64, under 64 MB in all")
     return ap.parse_args()
+
+
+DUMP_FEAT_ROWS = 8192          # 8,192 rows x 768 channels x 4 B = 25 MB
+DUMP_GRAD_ELEMS = 1 << 22      # 16 MB
+
+
+def dump_outputs(out_dir, feat, params, log):
+    """--dump-outputs: what the timed path hands its caller after a step -- the forward output and the parameters' gradients --
+    from the LAST timed step, so that two builds can be compared output for output.  The weights, the chunk and the cotangent
+    are seeded, and so are the sample positions: the same arguments give the same inputs and the same positions.
+      feat_rows.npy       (min(n, 8192), C) f32  output rows at seeded row indices (ascending)
+      feat_row_norms.npy  (n,) f64               L2 norm of every output row
+      grad_norms.npy      (P,) f64               L2 norm of every parameter's gradient, model.parameters() order (0: no gradient)
+      grad_sample.npy     (min(N, 4 Mi),) f32    gradient elements at seeded positions (ascending) of all parameters, flattened
+                                                 and concatenated in model.parameters() order (0: no gradient)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    f = feat.detach().float()
+    n = f.shape[0]
+    rows = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_FEAT_ROWS), replace=False))
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1) for p in params]
+    flat = torch.cat(grads)
+    pos = np.sort(np.random.default_rng(1).choice(flat.numel(), min(flat.numel(), DUMP_GRAD_ELEMS), replace=False))
+    arrays = {
+        "feat_rows": f[torch.from_numpy(rows).to(f.device)].cpu().numpy(),
+        "feat_row_norms": f.double().norm(dim=1).cpu().numpy(),
+        "grad_norms": torch.stack([g.double().norm() for g in grads]).cpu().numpy(),
+        "grad_sample": flat[torch.from_numpy(pos).to(flat.device)].cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("dumped the last timed step's outputs to %s: %s (%.1f MB)" % (
+        out_dir, ", ".join("%s %s %s" % (k, a.dtype, "x".join(map(str, a.shape))) for k, a in arrays.items()),
+        sum(a.nbytes for a in arrays.values()) / 1e6))
 
 
 def _probes_module():
@@ -610,7 +643,9 @@ def main():
         plan, state["plan"] = state["plan"], None
         t_b = time.perf_counter()
         try:
-            steady(plan, {"feat": data["feat"], "cot": cot16})
+            out_ = steady(plan, {"feat": data["feat"], "cot": cot16})
+            if args.dump_outputs:
+                state["out"] = out_            # (detached) kept for --dump-outputs: the last timed step's is written after the timing
         except CaptureInvalidated as e:
             # An invalidated capture cannot be ended, and this thread still owns it: the allocator keeps the capture's pool
             # registered, device-wide synchronisation and empty_cache() are refused from here on.  This PROCESS is done.  One rank:
@@ -707,6 +742,8 @@ def main():
     dt = time.perf_counter() - t0
     if plan_ahead is not None:
         plan_ahead.close()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state.pop("out")["feat"], list(model.parameters()), log)
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
