@@ -18,6 +18,8 @@
  *                                             layout and the qkv[order] gather in front of it (ptv3:172-188, 208-216)
  *   ss_lang_head_fwd / ss_lang_head_bwd       models/default.py:98-109 (F.normalize), losses/misc.py:254-270
  *                                             (CosineSimilarity), :274-295 (L2Loss)
+ *   ss_seg_loss_fwd / ss_seg_loss_bwd         losses/misc.py:35-62 (CrossEntropyLoss), losses/lovasz.py:121-256 (LovaszLoss, multiclass)
+ *   ss_seg_iou                                utils/misc.py:167-179 (intersection_and_union_gpu), hooks/evaluator.py:106-240
  *   ss_knn_query ... ss_bfs_cluster           libs/pointops/src/pointops_api.cpp:15-31,
  *                                             libs/pointops2/src/pointops_api.cpp:17-44,
  *                                             libs/pointgroup_ops/src/bfs_cluster.cpp:140-145
@@ -310,6 +312,27 @@ int ss_lang_head_fwd(const void* feat, int feat_dtype, const void* target, int t
 int ss_lang_head_bwd(const void* feat, int feat_dtype, const void* target, int target_dtype, const unsigned char* mask,
                      int normalize, const float* rowstat, const float* coef, const void* dp_extra, int dp_dtype,
                      void* dfeat, int dfeat_dtype, int64_t n, int channels, ss_stream_t stream);
+
+/* ---- semantic segmentation: CrossEntropyLoss + multiclass Lovasz-softmax, and the evaluator's counts (csrc/seg_loss.hip) -------
+ * logits (n, C) SS_DTYPE_*, C <= 256; labels (n) int64; a row is valid when its label != ignore_index and lies in [0, C) (the caller
+ * asserts the range).  All arithmetic fp32, no float atomics: two runs give bitwise-equal results.
+ * Forward: rowstat (n, 2) f32 = per-row max and sum of exp (kept for the backward); sums (4) f32 = [sum over valid rows of
+ *   -log softmax[label], #valid, sum over contributing classes of the Lovasz loss, #contributing classes].  A class contributes when
+ *   it has a valid foreground row and class_seen (C bytes, NULL = all) marks it.  lovasz = 0 skips the Lovasz part (glov / present
+ *   unused, sums[2..3] = 0); else glov (C, n) f32 = the Lovasz gradient with respect to each error (rows of non-contributing classes
+ *   are not written) and present (C) int32 = the contributing flags.  lovasz needs C * n < 2^31.  Workspace from the query.
+ * Backward: coef (2) f32 DEVICE values = dL/dsums[0], dL/dsums[2]; dlogits (n, C) in the logits' dtype (glov NULL: CE only).
+ * ss_seg_iou: out (3, C) int64 = [intersection, union, target] of intersection_and_union_gpu(pred, target, C, ignore_index), with
+ *   pred = the arg-max of the logits (equal maxima: the lowest class) or the given pred (n) int32. */
+size_t ss_seg_loss_workspace_bytes(int64_t n, int num_classes);
+int ss_seg_loss_fwd(const void* logits, int dtype, const int64_t* labels, int64_t n, int num_classes, int64_t ignore_index,
+                    const unsigned char* class_seen, int lovasz, float* rowstat, float* glov, int32_t* present, float* sums,
+                    void* workspace, size_t workspace_bytes, ss_stream_t stream);
+int ss_seg_loss_bwd(const void* logits, int dtype, const int64_t* labels, int64_t n, int num_classes, int64_t ignore_index,
+                    const float* rowstat, const float* glov, const int32_t* present, const float* coef, void* dlogits,
+                    ss_stream_t stream);
+int ss_seg_iou(const void* logits, int dtype, const int32_t* pred, const int64_t* target, int64_t n, int num_classes,
+               int64_t ignore_index, int64_t* out, ss_stream_t stream);
 
 /* ---- row movement ------------------------------------------------------------------------ */
 int ss_gather_rows(const void* src, const int32_t* idx, void* dst, int64_t n_dst, int64_t row_bytes, ss_stream_t stream);

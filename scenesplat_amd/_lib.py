@@ -106,6 +106,10 @@ PROTOTYPES = {
     "ss_lang_head_blocks": (c_i, [c_i64]),
     "ss_lang_head_fwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i64, c_i, c_p]),
     "ss_lang_head_bwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_i64, c_i, c_p]),
+    "ss_seg_loss_workspace_bytes": (c_sz, [c_i64, c_i]),
+    "ss_seg_loss_fwd": (c_i, [c_p, c_i, c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "ss_seg_loss_bwd": (c_i, [c_p, c_i, c_p, c_i64, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "ss_seg_iou": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_i64, c_p, c_p]),
     "ss_gather_rows": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_p]),
     "ss_scatter_rows": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_p]),
     "ss_gather_add_rows": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),

@@ -795,6 +795,66 @@ def lang_head_bwd(feat, target, mask, normalize, rowstat, coef, dp_extra):
     return dfeat
 
 
+# ---- semantic segmentation losses and metric ------------------------------------------------------------------
+SEG_MAX_CLASSES = 256
+
+
+def _seg_operands(logits, labels):
+    _req(logits, None, "logits")
+    if logits.dim() != 2 or not 1 <= logits.shape[1] <= SEG_MAX_CLASSES:
+        raise RuntimeError(f"seg_loss: logits must be (n, C) with C <= {SEG_MAX_CLASSES}")
+    n = logits.shape[0]
+    _req(labels, torch.int64, "labels", (n,))
+    return n, logits.shape[1]
+
+
+def seg_loss_fwd(logits, labels, ignore_index, class_seen=None, lovasz=True):
+    """logits (n, C) f32 | bf16, labels (n) int64 -> (sums (4) f32 = [ce_sum, n_valid, lovasz_sum, n_present], rowstat (n, 2),
+    glov (C, n) | None, present (C) int32 | None).  class_seen: (C) uint8 mask on the device or None."""
+    n, C = _seg_operands(logits, labels)
+    dev = logits.device
+    if class_seen is not None:
+        _req(class_seen, torch.uint8, "class_seen", (C,))
+    rowstat = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    glov = torch.empty((C, n), dtype=torch.float32, device=dev) if lovasz else None
+    present = torch.empty(C, dtype=torch.int32, device=dev) if lovasz else None
+    sums = torch.empty(4, dtype=torch.float32, device=dev)
+    ws = _ws(lib().ss_seg_loss_workspace_bytes(n, C), dev)
+    check(lib().ss_seg_loss_fwd(_p(logits), dtype_code(logits), _p(labels), n, C, int(ignore_index), _p(class_seen), int(bool(lovasz)),
+                                _p(rowstat), _p(glov), _p(present), _p(sums), _p(ws), ws.numel(), _stream()), "ss_seg_loss_fwd")
+    return sums, rowstat, glov, present
+
+
+def seg_loss_bwd(logits, labels, ignore_index, rowstat, glov, present, coef):
+    """-> dlogits (n, C) in the logits' dtype.  coef (2) f32 on the device = dL/d[ce_sum, lovasz_sum]."""
+    n, C = _seg_operands(logits, labels)
+    _req(rowstat, torch.float32, "rowstat", (n, 2)); _req(coef, torch.float32, "coef", (2,))
+    if glov is not None:
+        _req(glov, torch.float32, "glov", (C, n)); _req(present, torch.int32, "present", (C,))
+    dlogits = torch.empty_like(logits)
+    check(lib().ss_seg_loss_bwd(_p(logits), dtype_code(logits), _p(labels), n, C, int(ignore_index), _p(rowstat), _p(glov),
+                                _p(present), _p(coef), _p(dlogits), _stream()), "ss_seg_loss_bwd")
+    return dlogits
+
+
+def seg_iou(target, num_classes, ignore_index, logits=None, pred=None):
+    """-> (3, C) int64 [intersection, union, target] of intersection_and_union_gpu(pred | argmax(logits), target, C, ignore_index)."""
+    n = target.shape[0]
+    _req(target, torch.int64, "target", (n,))
+    C = int(num_classes)
+    if not 1 <= C <= SEG_MAX_CLASSES:
+        raise RuntimeError(f"seg_iou: 1 <= num_classes <= {SEG_MAX_CLASSES}")
+    if pred is not None:
+        _req(pred, torch.int32, "pred", (n,))
+        dt = F32
+    else:
+        _req(logits, None, "logits", (n, C))
+        dt = dtype_code(logits)
+    out = torch.empty((3, C), dtype=torch.int64, device=target.device)
+    check(lib().ss_seg_iou(_p(logits), dt, _p(pred), _p(target), n, C, int(ignore_index), _p(out), _stream()), "ss_seg_iou")
+    return out
+
+
 # ---- rows ------------------------------------------------------------------------------------
 def gather_rows(src, idx, out=None):
     """out[i] = src[idx[i]] (zero row where idx < 0).  src (m, C)."""

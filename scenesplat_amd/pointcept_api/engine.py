@@ -304,9 +304,9 @@ class Trainer(TrainerBase):
     """cfg: mapping with model / optimizer / scheduler / param_dicts / hooks / enable_amp / clip_grad /
     eval_epoch / save_path / find_unused_parameters [/ weight / resume / device].  The train loader is any
     sized iterable of input dicts (the reference builds a DataLoader from cfg.data; data loading is outside
-    the hot path, so it is injected: `train_loader=`)."""
+    the hot path, so it is injected: `train_loader=`, and the evaluation loader of SemSegEvaluator as `val_loader=`)."""
 
-    def __init__(self, cfg, train_loader=None, logger=None):
+    def __init__(self, cfg, train_loader=None, logger=None, val_loader=None):
         super().__init__()
         self.cfg = cfg
         self.max_epoch = cfg.get("eval_epoch", 1)
@@ -315,7 +315,7 @@ class Trainer(TrainerBase):
         self.device = torch.device(cfg.get("device", "cuda"))
         self.grad_exchange = None
         self.model = self.build_model()
-        self.train_loader, self.val_loader = train_loader, None
+        self.train_loader, self.val_loader = train_loader, val_loader
         self.optimizer = build_optimizer(cfg["optimizer"], self.model, cfg.get("param_dicts"))
         sched = dict(cfg["scheduler"])
         sched.setdefault("total_steps", max(1, len(train_loader)) * self.max_epoch)
@@ -475,7 +475,7 @@ class MultiDatasetTrainer(Trainer):
     scheduler's total_steps = iter_per_epoch x (max_epoch - start_epoch).  train_loader: a MultiDatasetLoader, or a list of
     (loader, ratio) pairs (ratio = the dataset's `loop` in the reference's config)."""
 
-    def __init__(self, cfg, train_loader=None, logger=None):
+    def __init__(self, cfg, train_loader=None, logger=None, val_loader=None):
         if not isinstance(train_loader, MultiDatasetLoader):
             pairs = list(train_loader or [])
             train_loader = MultiDatasetLoader([p[0] for p in pairs], [p[1] for p in pairs])
@@ -483,5 +483,5 @@ class MultiDatasetTrainer(Trainer):
         sched = dict(cfg["scheduler"])
         sched["total_steps"] = max(1, len(train_loader)) * (cfg.get("eval_epoch", 1) - 0)     # start_epoch is 0 before any resume
         cfg["scheduler"] = sched
-        super().__init__(cfg, train_loader=train_loader, logger=logger)
+        super().__init__(cfg, train_loader=train_loader, logger=logger, val_loader=val_loader)
         self.comm_info["iter_per_epoch"] = len(train_loader)
