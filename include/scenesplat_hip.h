@@ -270,10 +270,12 @@ int ss_add_layernorm_bwd(const void* g_xout, int g_xout_dtype, const void* g_xco
                          float* dgamma_part, float* dbeta_part, int64_t n, int channels, int nblocks, ss_stream_t stream);
 
 /* ---- fused BatchNorm1d (+ exact GELU when act = 1) over (n, C) rows; mean/rstd per channel from the caller --------
- * ss_col_stats: per-block partial column sums of (x - shift) and (x - shift)^2 -> psum/psq (nblocks, C) */
-int ss_col_stats(const void* x, int x_dtype, const float* shift, float* psum, float* psq, int64_t n, int channels,
+ * ss_col_stats: per-block partial column sums of (x - shift) and (x - shift)^2 -> psum/psq (nblocks, C), with shift = row 0 of x
+ * (a value of the batch conditions the one-pass variance whatever the column means are); shift_out (C f32, may be NULL) receives it */
+int ss_col_stats(const void* x, int x_dtype, float* shift_out, float* psum, float* psq, int64_t n, int channels,
                  int nblocks, ss_stream_t stream);
-/* ss_bn_stats_finish: (psum, psq) partials of ss_col_stats (stored as part (2, nblocks, C)) -> batch mean / rstd and, when
+/* ss_bn_stats_finish: (psum, psq) partials of ss_col_stats (stored as part (2, nblocks, C)) and its shift_out (NULL: the sums are
+ * of plain x) -> batch mean = shift + s/n, rstd = rsqrt(q/n - (s/n)^2 + eps) and, when
  * running_mean / running_var are given, nn.BatchNorm1d's training-mode update (momentum, unbiased variance; reference:
  * torch.nn.BatchNorm1d as used by pointcept/models/point_transformer_v3/point_transformer_v3m1_base.py:499-506,385-386);
  * num_batches (int64, may be NULL) is incremented.  ss_bn_bwd_finish: partials of ss_bn_act_bwd_reduce -> sums (2, C) =

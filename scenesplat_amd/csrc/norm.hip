@@ -442,10 +442,13 @@ __device__ __forceinline__ void col_partials_store(float4 (&a)[IT], float4 (&b)[
   }
 }
 
-// partial column sums of x and x^2 (shifted by `shift[c]` for conditioning; shift may be NULL)
+// partial column sums of (x - shift) and (x - shift)^2 with shift = row 0 of x: a value of the batch itself, so the one-pass
+// variance q/n - d^2 of ss_bn_stats_finish loses digits only to (mean - x[0])^2 / var (a few units), never to mean^2 / var -- the
+// running mean, the shift before, is 0 in a fresh model and trails the batch mean for hundreds of steps at momentum 0.01.
+// Every workgroup reads row 0 itself (one extra 16-byte load per lane); workgroup 0 writes it to shift_out (C f32, may be NULL).
 template <int IT>
 __global__ void __launch_bounds__(LN_THREADS)
-k_col_stats(const void* __restrict__ x, int x_dt, const float* __restrict__ shift, float* __restrict__ psum,
+k_col_stats(const void* __restrict__ x, int x_dt, float* __restrict__ shift_out, float* __restrict__ psum,
             float* __restrict__ psq, int64_t n, int C) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int waves_total = gridDim.x * (LN_THREADS / 64);
@@ -454,7 +457,10 @@ k_col_stats(const void* __restrict__ x, int x_dt, const float* __restrict__ shif
   for (int i = 0; i < IT; ++i) {
     s[i] = make_float4(0.f, 0.f, 0.f, 0.f); q[i] = s[i]; sh[i] = s[i];
     int j = i * 256 + lane * 4;
-    if (shift && j < C) sh[i] = *reinterpret_cast<const float4*>(shift + j);
+    if (n > 0 && j < C) {
+      sh[i] = ln_ld4(x, x_dt, j);
+      if (shift_out && blockIdx.x == 0 && wave == 0) *reinterpret_cast<float4*>(shift_out + j) = sh[i];
+    }
   }
   for (int64_t row = (int64_t)blockIdx.x * (LN_THREADS / 64) + wave; row < n; row += waves_total) {
 #pragma unroll
@@ -565,7 +571,8 @@ k_bn_act_bwd_apply(const void* __restrict__ dy, int dy_dt, const void* __restric
 }
 
 // ---- BatchNorm: the small vector work between the passes, one launch each way ---------------------------------------
-// Forward (training): per-block partial sums of (x - shift), (x - shift)^2  ->  batch mean / rstd, the running-statistics
+// Forward (training): per-block partial sums of (x - shift), (x - shift)^2 (shift = row 0 of the batch, as ss_col_stats left it)
+// ->  batch mean = shift + s/n, biased variance = q/n - (s/n)^2, rstd, the running-statistics
 // update of nn.BatchNorm1d (momentum, unbiased variance) and the batch counter.  PyTorch spells this as ~15 elementwise
 // launches on C-element vectors (s / n, shift + d, q / n - d^2, clamp, rsqrt, mul_, add_ ...) per BatchNorm layer.
 // (a block = 32 channels x 32 row groups: the nb <= 1024 partials of a channel are summed by 32 threads, then through LDS)
@@ -587,8 +594,8 @@ __device__ __forceinline__ void bnf_reduce(const float* __restrict__ part, int n
   }
 }
 __global__ void __launch_bounds__(BNF_THREADS)
-k_bn_stats_finish(const float* __restrict__ part, const float* shift /* may alias running_mean */, int nb, int C, float n,
-                  float unbias, float momentum, float eps, float* running_mean, float* __restrict__ running_var,
+k_bn_stats_finish(const float* __restrict__ part, const float* __restrict__ shift /* shift_out of ss_col_stats */, int nb, int C,
+                  float n, float unbias, float momentum, float eps, float* __restrict__ running_mean, float* __restrict__ running_var,
                   long long* __restrict__ num_batches, float* __restrict__ mean, float* __restrict__ rstd) {
   const int c = blockIdx.x * 32 + (threadIdx.x & 31), rg = threadIdx.x >> 5;
   if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches) *num_batches += 1;
@@ -618,11 +625,11 @@ k_bn_bwd_finish(const float* __restrict__ part, int nb, int C, float n, float* _
 
 #define SS_IT_SWITCH(MACRO) switch (it) { case 1: MACRO(1); break; case 2: MACRO(2); break; case 3: MACRO(3); break; default: MACRO(4); break; }
 
-extern "C" int ss_col_stats(const void* x, int x_dtype, const float* shift, float* psum, float* psq, int64_t n, int channels,
+extern "C" int ss_col_stats(const void* x, int x_dtype, float* shift_out, float* psum, float* psq, int64_t n, int channels,
                             int nblocks, hipStream_t stream) {
   if (n < 0 || channels <= 0 || (channels & 3) || channels > LN_MAXIT * 256 || nblocks < 1) return SS_ERR_ARG;
   const int it = (channels + 255) / 256;
-#define SS_CS(ITN) SS_LAUNCH(k_col_stats<ITN>, dim3(nblocks), dim3(LN_THREADS), 0, stream, x, x_dtype, shift, psum, psq, n, channels)
+#define SS_CS(ITN) SS_LAUNCH(k_col_stats<ITN>, dim3(nblocks), dim3(LN_THREADS), 0, stream, x, x_dtype, shift_out, psum, psq, n, channels)
   SS_IT_SWITCH(SS_CS)
 #undef SS_CS
   return SS_OK;

@@ -1010,8 +1010,7 @@ class _BatchNormAct(torch.autograd.Function):
                 mean, rstd = nv.bn_batch_stats(x, running_mean, running_var, num_batches, momentum, eps)
         else:
             if training:
-                shift = running_mean.float().contiguous()              # conditioning of the one-pass variance
-                s, q = nv.col_stats(x, shift)
+                shift, s, q = nv.col_stats(x)                          # sums of x - x[0]: the batch conditions its one-pass variance
                 d = s / n
                 mean = shift + d
                 var = (q / n - d * d).clamp_(min=0.0)

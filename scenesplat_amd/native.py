@@ -671,32 +671,36 @@ def add_layernorm_bwd(g_xout, g_xcopy, g_h, v, mean, rstd, gamma, rowscale, gx_d
 
 
 # ---- fused batchnorm (+GELU) ----------------------------------------------------------------------
-def col_stats(x, shift=None):
-    """-> (sum, sumsq) of (x - shift) per column, fp32 (partials reduced here)."""
+def col_stats(x):
+    """-> (shift, sum, sumsq): shift = row 0 of x (fp32) and the column sums of (x - shift), (x - shift)^2, fp32 (partials
+    reduced here).  mean = shift + sum / n; biased variance = sumsq / n - (sum / n)^2."""
     n, C = x.shape
     _req(x, None, "x")
     nb = lib().ss_add_layernorm_bwd_blocks(n)
     part = torch.empty((2, nb, C), dtype=torch.float32, device=x.device)
-    ps, pq = part[0], part[1]
-    check(lib().ss_col_stats(_p(x), _dt(x), _p(shift), _p(ps), _p(pq), n, C, nb, _stream()), "ss_col_stats")
+    shift = torch.empty(C, dtype=torch.float32, device=x.device)
+    check(lib().ss_col_stats(_p(x), _dt(x), _p(shift), _p(part[0]), _p(part[1]), n, C, nb, _stream()), "ss_col_stats")
     red = part.sum(1)
-    return red[0], red[1]
+    return shift, red[0], red[1]
 
 
 def bn_batch_stats(x, running_mean, running_var, num_batches, momentum, eps):
     """Training-mode BatchNorm statistics in two launches: -> (mean, rstd) of the batch (fp32, biased variance), with the
     running statistics (fp32 buffers, in place; momentum update with the unbiased variance) and the batch counter updated
-    the way nn.BatchNorm1d does.  running_mean also conditions the one-pass variance (sums of x - running_mean)."""
+    the way nn.BatchNorm1d does.  The one-pass variance is conditioned on the batch itself: the statistics pass sums
+    x - x[0] per column and hands row 0 to the finishing launch, so the result does not depend on how far the running
+    mean is from the batch mean (it is 0 in a fresh model)."""
     n, C = x.shape
     _req(x, None, "x")
     _req(running_mean, torch.float32, "running_mean", (C,)); _req(running_var, torch.float32, "running_var", (C,))
     nb = lib().ss_add_layernorm_bwd_blocks(n)
     part = torch.empty((2, nb, C), dtype=torch.float32, device=x.device)
-    check(lib().ss_col_stats(_p(x), _dt(x), _p(running_mean), _p(part[0]), _p(part[1]), n, C, nb, _stream()), "ss_col_stats")
-    out = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    small = torch.empty((3, C), dtype=torch.float32, device=x.device)             # shift | mean | rstd
+    shift, out = small[0], small[1:]
+    check(lib().ss_col_stats(_p(x), _dt(x), _p(shift), _p(part[0]), _p(part[1]), n, C, nb, _stream()), "ss_col_stats")
     if num_batches is not None:
         _req(num_batches, torch.int64, "num_batches_tracked")
-    check(lib().ss_bn_stats_finish(_p(part), _p(running_mean), nb, C, n, float(momentum), float(eps), _p(running_mean),
+    check(lib().ss_bn_stats_finish(_p(part), _p(shift), nb, C, n, float(momentum), float(eps), _p(running_mean),
                                    _p(running_var), _p(num_batches), _p(out[0]), _p(out[1]), _stream()), "ss_bn_stats_finish")
     return out[0], out[1]
 
