@@ -90,6 +90,23 @@ int ss_window_attn_bwd(const void* qkv, const void* out, const void* dout, const
 int ss_cast_bf16_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
 int ss_cast_bf16_group_elems_per_workgroup(void);
 
+/* ---- optimizer step: global gradient norm + AdamW update of all tensors of all parameter groups (replaces
+ * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step, pointcept/engines/train.py:196-232).  Grouped launches as above:
+ * wg_start (nprob + 1) at ss_optim_group_elems_per_workgroup() elements per workgroup; flags bit 0 = every pointer of the row is
+ * 16-byte aligned (16-byte lanes; otherwise one element per lane).  No atomics: results are bitwise reproducible.
+ * ss_grad_sqnorm_group: desc 3 int64 per tensor {g f32 pointer, numel, flags}; partials[w] = fp64 sum of squares of workgroup w.
+ * ss_grad_norm_finish:  record[0] = total_norm = sqrt(sum of partials), record[1] = coef = min(1, max_norm / (total_norm + 1e-6)),
+ *                       non-finite values propagating as in clip_grad_norm_(norm_type=2, error_if_nonfinite=False).
+ * ss_adamw_group:       desc 10 int64 per tensor {p, g, m, v f32 pointers, numel, flags, then 8 fp32: 1 - lr*wd, 1 - beta1, beta2,
+ *                       1 - beta2, sqrt(1 - beta2^t), eps, lr / (1 - beta1^t), 0}; record as written by ss_grad_norm_finish (its
+ *                       coef scales g on the fly) or NULL for coef = 1.  Writes p, m, v; g is only read. */
+int ss_optim_group_elems_per_workgroup(void);
+int ss_grad_sqnorm_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, double* partials,
+                         ss_stream_t stream);
+int ss_grad_norm_finish(const double* partials, int num_partials, float max_norm, float* record, ss_stream_t stream);
+int ss_adamw_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, const float* record,
+                   ss_stream_t stream);
+
 /* ---- DropPath row scales (timm DropPath on (n, C) rows, ptv3:333-336) ------------------------------------
  * out[i] = Bernoulli(keep[i]) / keep[i] for the n rows of all residual seams of a forward; Philox4x32-10, counter = row index,
  * key = the 64-bit seed read from DEVICE memory (so a captured launch draws fresh masks per replay). */

@@ -1088,3 +1088,87 @@ def cast_bf16_group(srcs, dsts):
         starts.append(starts[-1] + (s.numel() + per - 1) // per)
     d_dev, s_dev = _upload_descriptors(desc, starts, dev)
     check(lib().ss_cast_bf16_group(_p(d_dev), _p(s_dev), len(srcs), starts[-1], _stream()), "ss_cast_bf16_group")
+
+
+# ---- optimizer step: global gradient norm + grouped AdamW update (csrc/optim.hip) ----------------------------------------------
+_NORM_PARTIALS = {}     # device -> fp64 partial sums of the norm kernel, one per workgroup (grown on demand, reused every step)
+
+
+def _norm_partials(dev, n):
+    buf = _NORM_PARTIALS.get(dev)
+    if buf is None or buf.numel() < n:
+        buf = torch.empty(max(int(n), 1024), dtype=torch.float64, device=dev)
+        _NORM_PARTIALS[dev] = buf
+    return buf
+
+
+def _optim_check(t, n, dev, name):
+    """A tensor a grouped optimizer kernel may touch through its raw pointer: dense fp32, contiguous, n elements, on `dev`."""
+    _req(t, torch.float32, name)
+    if t.layout is not torch.strided or t.device != dev or (n is not None and t.numel() != n):
+        raise RuntimeError(f"{name}: expected a dense tensor" + (f" of {n} elements" if n is not None else "") + f" on {dev}")
+
+
+def _optim_starts(numels):
+    per = lib().ss_optim_group_elems_per_workgroup()
+    starts = [0]
+    for n in numels:
+        starts.append(starts[-1] + (n + per - 1) // per)
+    if starts[-1] >= 2 ** 31:
+        raise RuntimeError("grouped optimizer launch: more than 2^31 workgroups")
+    return starts
+
+
+def grad_norm_group(grads, max_norm, record=None):
+    """-> record (2,) fp32 on the device: [total_norm, coef] with total_norm the 2-norm over ALL of `grads` and
+    coef = min(1, max_norm / (total_norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s arithmetic.  Two launches, no host read;
+    the gradients are only read.  `record`: an existing (2,) fp32 tensor to write into."""
+    import numpy as np
+    if record is not None:
+        dev = _req(record, torch.float32, "record", (2,)).device
+    else:
+        dev = _req(grads[0], None, "grads[0]").device if len(grads) else torch.device("cuda", torch.cuda.current_device())
+        record = torch.empty(2, dtype=torch.float32, device=dev)
+    for j, g in enumerate(grads):
+        _optim_check(g, None, dev, f"grads[{j}]")
+    grads = [g for g in grads if g.numel()]                  # (an empty tensor adds nothing and owns no workgroup)
+    starts = _optim_starts([g.numel() for g in grads])
+    partials = _norm_partials(dev, starts[-1])
+    if grads:
+        desc = np.empty((len(grads), 3), dtype=np.int64)
+        desc[:, 0], desc[:, 1] = [g.data_ptr() for g in grads], [g.numel() for g in grads]
+        desc[:, 2] = (desc[:, 0] & 15) == 0                  # bit 0: 16-byte lanes
+        d_dev, s_dev = _upload_descriptors(desc, starts, dev)
+        check(lib().ss_grad_sqnorm_group(_p(d_dev), _p(s_dev), len(grads), starts[-1], _p(partials), _stream()), "ss_grad_sqnorm_group")
+    check(lib().ss_grad_norm_finish(_p(partials), starts[-1], float(max_norm), _p(record), _stream()), "ss_grad_norm_finish")
+    return record
+
+
+def adamw_group(rows, record=None):
+    """ONE launch: the AdamW update of every row (p, g, m, v, scalars) with scalars = (1 - lr*wd, 1 - beta1, beta2, 1 - beta2,
+    sqrt(1 - beta2^t), eps, lr / (1 - beta1^t)) computed by the caller in double.  p, m, v are updated in place, g is only read;
+    `record` (from grad_norm_group) scales g by its clip coefficient on the fly, None means no clipping."""
+    import numpy as np
+    if not len(rows):
+        return
+    dev = _req(rows[0][0], torch.float32, "rows[0].p").device
+    if record is not None and _req(record, torch.float32, "record", (2,)).device != dev:
+        raise RuntimeError("record: must live on the parameters' device")
+    for j, (p, g, m, v, s) in enumerate(rows):
+        for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+            _optim_check(t, p.numel(), dev, f"rows[{j}].{nm}")
+        if len(s) != 7:
+            raise RuntimeError(f"rows[{j}]: 7 scalars per row")
+    rows = [r for r in rows if r[0].numel()]
+    if not rows:
+        return
+    n = len(rows)
+    starts = _optim_starts([r[0].numel() for r in rows])
+    desc = np.zeros((n, 10), dtype=np.int64)
+    for k in range(4):
+        desc[:, k] = [r[k].data_ptr() for r in rows]
+    desc[:, 4] = [r[0].numel() for r in rows]
+    desc[:, 5] = ((desc[:, 0] | desc[:, 1] | desc[:, 2] | desc[:, 3]) & 15) == 0        # bit 0: 16-byte lanes
+    desc[:, 6:].view(np.float32)[:, :7] = np.asarray([r[4] for r in rows], dtype=np.float64)   # fp32 over the last four words
+    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
+    check(lib().ss_adamw_group(_p(d_dev), _p(s_dev), n, starts[-1], _p(record), _stream()), "ss_adamw_group")

@@ -19,12 +19,14 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from ..optim import FusedAdamW
 from .registry import HOOKS, MODELS, TRAINERS, Registry
 
 OPTIMIZERS = Registry("optimizers")
 OPTIMIZERS.register_module(module=torch.optim.SGD, name="SGD")
 OPTIMIZERS.register_module(module=torch.optim.Adam, name="Adam")
 OPTIMIZERS.register_module(module=torch.optim.AdamW, name="AdamW")
+OPTIMIZERS.register_module(module=FusedAdamW, name="FusedAdamW")   # opt-in: clipping + update in grouped HIP launches (optim.py)
 SCHEDULERS = Registry("schedulers")
 
 
@@ -317,6 +319,8 @@ class Trainer(TrainerBase):
         self.model = self.build_model()
         self.train_loader, self.val_loader = train_loader, val_loader
         self.optimizer = build_optimizer(cfg["optimizer"], self.model, cfg.get("param_dicts"))
+        if isinstance(self.optimizer, FusedAdamW) and cfg.get("clip_grad") is not None and self.optimizer.max_grad_norm is None:
+            self.optimizer.max_grad_norm = float(cfg["clip_grad"])     # the optimizer clips inside its own step (run_step skips clip_grad_norm_)
         sched = dict(cfg["scheduler"])
         sched.setdefault("total_steps", max(1, len(train_loader)) * self.max_epoch)
         self.scheduler = build_scheduler(sched, self.optimizer)
@@ -409,7 +413,7 @@ class Trainer(TrainerBase):
                 and hasattr(getattr(self.model, "backbone", self.model), "prepare_plan") and "grid_coord" in inp):
             inp["epoch_progress"] = self.epoch / self.max_epoch
             out = self._steady_run_step(inp, amp)
-            if self.cfg.get("clip_grad") is not None:
+            if self.cfg.get("clip_grad") is not None and getattr(self.optimizer, "max_grad_norm", None) is None:
                 torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.cfg["clip_grad"])
             self.optimizer.step()
             self.scheduler.step()
@@ -423,7 +427,7 @@ class Trainer(TrainerBase):
         loss.backward()
         if self.grad_exchange is not None:
             self.grad_exchange.finish()
-        if self.cfg.get("clip_grad") is not None:
+        if self.cfg.get("clip_grad") is not None and getattr(self.optimizer, "max_grad_norm", None) is None:
             torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.cfg["clip_grad"])
         self.optimizer.step()
         self.scheduler.step()
