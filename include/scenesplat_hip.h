@@ -141,6 +141,27 @@ int ss_window_attn_hm_bwd(const void* hm, const void* out, const void* dout, con
                           int64_t n_pad, int channels, int num_heads, float scale, void* dqkv, void* workspace,
                           size_t workspace_bytes, ss_stream_t stream);
 
+/* ---- window attention with relative position encoding (PT-v3m1 enable_rpe; csrc/attention_rpe.hip) ----------------
+ * ss_window_attn_fwd / _bwd with a learned bias added to every score before the softmax:
+ *   bias[h][i][j] = sum over the axes a of table[a * rpe_num + clamp(g_i[a] - g_j[a], -pos_bnd, pos_bnd) + pos_bnd][h],
+ * g = grid_coord[gidx[slot]], rpe_num = 2 * pos_bnd + 1 (0 <= pos_bnd <= 64).  grid_coord (n, 3) int32; table (3 * rpe_num,
+ * num_heads) f32; the bias is not multiplied by `scale`; lse includes it.  impl = SS_ATTN_MFMA (bf16) runs head dims
+ * 16/32/48/64 and windows up to 2048 on the matrix cores; longer windows and other shapes run on the SIMT kernels.
+ * Backward: dqkv as ss_window_attn_bwd; dtable (3 * rpe_num, num_heads) f32 is OVERWRITTEN with the gradient of the table
+ * (no global atomics: per-workgroup partial sums in the workspace, added in a fixed order; a row no (query, key) pair
+ * indexes is exactly 0).  The workspace needs no initialisation. */
+int ss_window_attn_rpe_fwd(const void* qkv, const int32_t* gidx, const int32_t* sidx, const int32_t* win_start,
+                           int num_windows, int max_window, int64_t n, int64_t n_pad, int channels, int num_heads,
+                           float scale, int dtype, int impl, const int32_t* grid_coord, const float* table, int pos_bnd,
+                           void* out, float* lse, ss_stream_t stream);
+size_t ss_window_attn_rpe_bwd_workspace_bytes(int64_t n, int64_t n_pad, int channels, int num_heads, int dtype,
+                                              int num_windows, int max_window, int pos_bnd);
+int ss_window_attn_rpe_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const int32_t* gidx,
+                           const int32_t* sidx, const int32_t* win_start, int num_windows, int max_window, int64_t n,
+                           int64_t n_pad, int channels, int num_heads, float scale, int dtype, int impl,
+                           const int32_t* grid_coord, const float* table, int pos_bnd, void* dqkv, float* dtable,
+                           void* workspace, size_t workspace_bytes, ss_stream_t stream);
+
 /* ---- submanifold convolution ------------------------------------------------------------ */
 /* nbr (k^3, n) int32 (tap-major), -1 = no site; zkeys_sorted/zorder: z (or z-trans, swap_xy=1) codes sorted */
 int ss_subm_rulebook(const int32_t* grid_coord, const int32_t* batch, int64_t n, int depth,

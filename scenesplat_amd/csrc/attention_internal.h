@@ -19,3 +19,6 @@ int ss_attn_bwd_mfma(const void* qkv, const void* dout, const void* out, const f
 // 32x32x16 re-tiling of the forward (attention_mfma32.hip); same contract as ss_attn_fwd_mfma
 int ss_attn_fwd_mfma32(const void* qkv, const int32_t* gidx, const int32_t* sidx, const int32_t* win_start, int W,
                        int max_window, void* out, float* lse, int C, int H, float scale, hipStream_t st);
+// attention_rpe.hip (relative position encoding; C-ABI entry points ss_window_attn_rpe_* live in that file and reuse
+// ss_attn_delta / ss_attn_fix_borrowed above): largest pos_bnd whose 3 * (2 * pos_bnd + 1) table column fits the kernels' LDS copy
+#define SS_ATTN_RPE_MAX_POS_BND 64   // patch sizes up to 8192

@@ -37,6 +37,33 @@ def window_attention(qkv, win, num_heads, scale, impl=nv.ATTN_SIMT):
     return _WindowAttention.apply(qkv, win, num_heads, scale, impl)
 
 
+class _WindowAttentionRPE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, table, win, grid_coord, pos_bnd, num_heads, scale, impl):
+        qkv = qkv.contiguous()
+        tab = table.detach().float().contiguous()
+        out, lse = nv.window_attn_rpe_fwd(qkv, win, grid_coord, tab, pos_bnd, num_heads, scale, impl)
+        ctx.save_for_backward(qkv, out, lse, tab)
+        ctx.win, ctx.grid_coord, ctx.pos_bnd, ctx.num_heads, ctx.scale, ctx.impl = win, grid_coord, pos_bnd, num_heads, scale, impl
+        ctx.table_dtype = table.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, tab = ctx.saved_tensors
+        dqkv, dtable = nv.window_attn_rpe_bwd(qkv, out, dout.contiguous().to(qkv.dtype), lse, ctx.win, ctx.grid_coord, tab,
+                                              ctx.pos_bnd, ctx.num_heads, ctx.scale, ctx.impl)
+        return dqkv, dtable.to(ctx.table_dtype), None, None, None, None, None, None
+
+
+def window_attention_rpe(qkv, win, grid_coord, table, pos_bnd, num_heads, scale, impl=nv.ATTN_SIMT):
+    """window_attention with PTv3's relative position encoding (ptv3:29-48, 199-201): the bias
+    table[clamp(g_i - g_j, -pos_bnd, pos_bnd) + pos_bnd] summed over the three axes is added to every score before the softmax,
+    inside the kernels (csrc/attention_rpe.hip).  grid_coord (n, 3) int32 in memory row order; table (3 * (2 * pos_bnd + 1),
+    num_heads).  Gradients: qkv and table."""
+    return _WindowAttentionRPE.apply(qkv, table, win, grid_coord, pos_bnd, num_heads, scale, impl)
+
+
 class _SegmentMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src, level, mean):

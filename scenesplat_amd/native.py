@@ -970,7 +970,53 @@ def window_attn_bwd(qkv, out, dout, lse, win, num_heads, scale, impl):
     return dqkv
 
 
-# ---- head-major window attention (csrc/attention_hm.hip, round 3) ------------------------------------------------------
+# ---- window attention with relative position encoding (csrc/attention_rpe.hip) -----------------
+def _req_rpe(qkv, win, num_heads, grid_coord, table, pos_bnd):
+    n, C3 = qkv.shape
+    _req(qkv, None, "qkv")
+    if n != win.n:
+        raise RuntimeError(f"qkv rows {n} != window index rows {win.n}")
+    pos_bnd = int(pos_bnd)
+    _req(grid_coord, torch.int32, "grid_coord", (n, 3))
+    _req(table, torch.float32, "table", (3 * (2 * pos_bnd + 1), num_heads))
+    return n, C3 // 3, pos_bnd
+
+
+def window_attn_rpe_fwd(qkv, win, grid_coord, table, pos_bnd, num_heads, scale, impl):
+    """window_attn_fwd with the RPE bias table[clamp(g_i - g_j) + pos_bnd] (three axes) added to every score."""
+    n, C, pos_bnd = _req_rpe(qkv, win, num_heads, grid_coord, table, pos_bnd)
+    out = torch.empty((n, C), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((win.n_pad, num_heads), dtype=torch.float32, device=qkv.device)
+    check(lib().ss_window_attn_rpe_fwd(_p(qkv), _p(win.gidx), _p(win.sidx), _p(win.win_start), win.num_windows,
+                                       win.max_window, n, win.n_pad, C, num_heads, float(scale), dtype_code(qkv), int(impl),
+                                       _p(grid_coord), _p(table), pos_bnd, _p(out), _p(lse), _stream()),
+          "ss_window_attn_rpe_fwd")
+    return out, lse
+
+
+def window_attn_rpe_bwd_workspace_bytes(qkv, win, num_heads, pos_bnd):
+    n, C3 = qkv.shape
+    return lib().ss_window_attn_rpe_bwd_workspace_bytes(n, win.n_pad, C3 // 3, num_heads, dtype_code(qkv), win.num_windows,
+                                                        win.max_window, int(pos_bnd))
+
+
+def window_attn_rpe_bwd(qkv, out, dout, lse, win, grid_coord, table, pos_bnd, num_heads, scale, impl, workspace=None):
+    """-> (dqkv, dtable fp32).  `workspace`: optional uint8 buffer of window_attn_rpe_bwd_workspace_bytes (any content)."""
+    n, C, pos_bnd = _req_rpe(qkv, win, num_heads, grid_coord, table, pos_bnd)
+    _req(out, qkv.dtype, "out", (n, C)); _req(dout, qkv.dtype, "dout", (n, C))
+    _req(lse, torch.float32, "lse", (win.n_pad, num_heads))
+    dqkv = torch.empty_like(qkv)
+    dtable = torch.empty_like(table)
+    nb = window_attn_rpe_bwd_workspace_bytes(qkv, win, num_heads, pos_bnd)
+    ws = _ws(nb, qkv.device) if workspace is None else _req(workspace, torch.uint8, "workspace")
+    check(lib().ss_window_attn_rpe_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(win.gidx), _p(win.sidx), _p(win.win_start),
+                                       win.num_windows, win.max_window, n, win.n_pad, C, num_heads, float(scale),
+                                       dtype_code(qkv), int(impl), _p(grid_coord), _p(table), pos_bnd, _p(dqkv), _p(dtable),
+                                       _p(ws), ws.numel(), _stream()), "ss_window_attn_rpe_bwd")
+    return dqkv, dtable
+
+
+# ---- head-major window attention (csrc/attention_hm.hip, round 3)------------------------------------------------------
 LOG2E = 1.4426950408889634
 
 

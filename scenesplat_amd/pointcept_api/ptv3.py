@@ -112,23 +112,62 @@ def _lin(mod, x):
     return SF.linear(x, mod.weight, mod.bias)
 
 
+class RPE(nn.Module):
+    """Relative position encoding table of the reference (ptv3:29-48): parameter holder with its key (`rpe_table`), shape and
+    initialisation.  Parameter only: the lookup runs inside the attention kernels (csrc/attention_rpe.hip)."""
+
+    def __init__(self, patch_size, num_heads):
+        super().__init__()
+        self.patch_size, self.num_heads = patch_size, num_heads
+        self.pos_bnd = int((4 * patch_size) ** (1 / 3) * 2)      # evaluated as the reference does: 1024 -> 31, not 32
+        self.rpe_num = 2 * self.pos_bnd + 1
+        self.rpe_table = nn.Parameter(torch.zeros(3 * self.rpe_num, num_heads))
+        nn.init.trunc_normal_(self.rpe_table, std=0.02)
+
+
 class SerializedAttention(PointModule):
     def __init__(self, channels, num_heads, patch_size, qkv_bias=True, qk_scale=None, attn_drop=0.0,
                  proj_drop=0.0, order_index=0, enable_rpe=False, enable_flash=True, upcast_attention=True,
                  upcast_softmax=True):
         super().__init__()
         assert channels % num_heads == 0
-        if enable_rpe:
-            raise NotImplementedError("enable_rpe is off in every SceneSplat language config; not on the HIP path")
+        if enable_rpe and enable_flash:
+            raise AssertionError("Set enable_rpe to False when enable Flash Attention")      # the reference's assertion
         if attn_drop != 0.0 or proj_drop != 0.0:
             raise NotImplementedError("attention / projection dropout are 0 in the reference configs")
         self.channels, self.num_heads, self.patch_size = channels, num_heads, patch_size
         self.scale = qk_scale or (channels // num_heads) ** -0.5
         self.order_index = order_index
+        self.enable_rpe = bool(enable_rpe)
         self.qkv = nn.Linear(channels, channels * 3, bias=qkv_bias)
         self.proj = nn.Linear(channels, channels)
+        self.rpe = RPE(patch_size, num_heads) if enable_rpe else None
+
+    def rpe_window_size(self, level):
+        """Window length of the RPE mode, the reference's non-flash rule (ptv3:173-176): min(smallest batch element, patch_size),
+        so that every window is exactly that long.  From the level's host-side offsets: no device sync."""
+        k = min(min(level.counts), self.patch_size)
+        if k < 1:
+            raise ValueError("enable_rpe: every batch element needs at least one point")
+        return k
+
+    def _forward_rpe(self, x, level):
+        win = level.window(self.order_index, self.rpe_window_size(level))
+        qkv = _lin(self.qkv, x)
+        bf16 = (x.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16) \
+            or qkv.dtype == torch.bfloat16
+        if bf16 and (self.channels // self.num_heads) in (16, 32, 48, 64):
+            impl = nv.ATTN_MFMA          # the library itself sends windows the MFMA kernels do not cover to the SIMT pair
+        else:
+            impl = nv.ATTN_SIMT
+        a = qkv.to(torch.bfloat16) if bf16 else qkv
+        feat = SF.window_attention_rpe(a, win, level.grid_coord, self.rpe.rpe_table, self.rpe.pos_bnd, self.num_heads,
+                                       self.scale, impl).to(qkv.dtype)
+        return _lin(self.proj, feat)
 
     def forward(self, x, level):
+        if self.enable_rpe:
+            return self._forward_rpe(x, level)
         win = level.window(self.order_index, self.patch_size)
         impl = RUNTIME["attn_impl"]
         if (impl == nv.ATTN_MFMA and RUNTIME.get("attn_headmajor", True) and x.is_cuda and torch.is_autocast_enabled()
@@ -404,12 +443,16 @@ class PointTransformerV3(PointModule):
             enc = getattr(self.enc, f"enc{s}")
             ks.append((s, 3, walk[s]))
             for i in range(self.enc_depths[s]):
-                wins.append((s, i % K, getattr(enc, f"block{i}").attn.patch_size))
+                attn = getattr(enc, f"block{i}").attn
+                if not attn.enable_rpe:          # RPE windows follow the batch (rpe_window_size): built on first use
+                    wins.append((s, i % K, attn.patch_size))
         if not self.cls_mode:
             for s in range(self.num_stages - 1):
                 dec = getattr(self.dec, f"dec{s}")
                 for i in range(self.dec_depths[s]):
-                    wins.append((s, i % K, getattr(dec, f"block{i}").attn.patch_size))
+                    attn = getattr(dec, f"block{i}").attn
+                    if not attn.enable_rpe:
+                        wins.append((s, i % K, attn.patch_size))
         return wins, ks
 
     def prepare_plan(self, data_dict, perms=None, stream=None):
