@@ -20,6 +20,8 @@
  *                                             (CosineSimilarity), :274-295 (L2Loss)
  *   ss_seg_loss_fwd / ss_seg_loss_bwd         losses/misc.py:35-62 (CrossEntropyLoss), losses/lovasz.py:121-256 (LovaszLoss, multiclass)
  *   ss_seg_iou                                utils/misc.py:167-179 (intersection_and_union_gpu), hooks/evaluator.py:106-240
+ *   ss_aug_bbox ... ss_aug_color             pointcept/datasets/transform.py:446-816,1120-1178 (the per-sample augmentations
+ *                                             in front of GridSample: CenterShift ... ChromaticJitter)
  *   ss_knn_query ... ss_bfs_cluster           libs/pointops/src/pointops_api.cpp:15-31,
  *                                             libs/pointops2/src/pointops_api.cpp:17-44,
  *                                             libs/pointgroup_ops/src/bfs_cluster.cpp:140-145
@@ -398,6 +400,35 @@ int ss_segment_minmax_bwd(const void* dout, const int32_t* arg, void* dsrc, int6
 int ss_segment_bcast(const void* dout, const int32_t* cluster, const int32_t* idx_ptr, void* dsrc, int64_t n,
                      int channels, int dtype, int mean, ss_stream_t stream);
 
+
+/* ---- per-sample Gaussian augmentations (csrc/augment.hip) ------------------------------------------------------------------
+ * One pass over HBM each, fp32, in place.  Pointers named `h_*` are HOST pointers to a few floats that travel as kernel arguments
+ * (NULL = that part is off); everything else is a device pointer. */
+/* out6 = {min x, min y, min z, max x, max y, max z} of A x + b (h_affine = A row-major (9) then b (3)) or of x itself (h_affine
+ * NULL: exact).  Deterministic: per-block partials (ss_aug_bbox_blocks(n) * 6 floats) and a finish step, no atomics.  n >= 1. */
+int ss_aug_bbox_blocks(int64_t n);
+int ss_aug_bbox(const float* x, int64_t n, const float* h_affine, float* partials, float* out6, ss_stream_t stream);
+/* The fused rigid pass of CenterShift / RandomRotate / RandomScale / RandomShift / RandomFlip / RandomJitter.  coord (n,3), quat (n,4,
+ * wxyz), scale (n,3), normal (n,3): each optional (NULL = absent).
+ *   coord  <- A x + b (h_affine; NULL = identity), then + clip(sigma * N(0,1), +-clip) per component when jitter != 0: N from
+ *             noise (n,3) when given, else Philox4x32-10 keyed by seed with the point index as counter (Box-Muller)
+ *   quat   <- normalise, r (x) q (h_rquat, unit, wxyz; Hamilton product), then for flip (bit 0: x, bit 1: y) the conjugation
+ *             F R F = (w, x, -y, -z) | (w, -x, y, -z) | (w, -x, -y, z) and the sign that scipy's Rotation.from_matrix gives: the
+ *             component that wins arg-max [M00, M11, M22, trace] (for a unit quaternion: the first largest of x^2, y^2, z^2, w^2)
+ *             is made positive.  Rows of zero norm are left unchanged.
+ *   scale  <- scale * h_scale_mul (3)
+ *   normal <- L normal (h_lin, row-major 9: rotation and reflection only) */
+int ss_aug_gaussians(float* coord, float* quat, float* scale, float* normal, int64_t n, const float* h_affine,
+                     const float* h_rquat, int flip, const float* h_scale_mul, const float* h_lin, int jitter, float jitter_sigma,
+                     float jitter_clip, const float* noise, uint64_t seed, ss_stream_t stream);
+/* ElasticDistortion's application: coord += trilinear(noise, coord) * magnitude; noise (d0,d1,d2,3), node i of an axis at
+ * origin + i * granularity, 0 outside the grid */
+int ss_aug_elastic(float* coord, int64_t n, const float* noise, int d0, int d1, int d2, const float* h_origin, float granularity,
+                   float magnitude, ss_stream_t stream);
+/* color (n,3) on the 0..255 scale.  flags bit 0: c <- (1 - blend) c + blend (c - lo) 255 / (hi - lo); bit 1: c <- clip(c + tr, 0, 255);
+ * bit 2: c <- clip(c + N * jitter_std * 255, 0, 255), N from noise (n,3) or Philox (as above); then normalize != 0: c / 127.5 - 1 */
+int ss_aug_color(float* color, int64_t n, int flags, const float* h_lo, const float* h_hi, float blend, const float* h_tr,
+                 float jitter_std, const float* noise, uint64_t seed, int normalize, ss_stream_t stream);
 
 /* ---- libs/pointops, pointops2, pointgroup_ops (fp32 features, int32 indices, offset batches) ------- */
 /* libs/pointops/src/knn_query/knn_query_cuda.cpp:7-16; nsample <= 128; idx -1 / dist2 1e10 padding */

@@ -3,7 +3,7 @@
 #include "attention_internal.h"
 #include "../../include/scenesplat_hip.h"
 
-extern "C" int ss_version(void) { return 100; }
+extern "C" int ss_version(void) { return 101; }
 
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 

@@ -457,17 +457,7 @@ extern "C" int ss_cast_bf16_group(const int64_t* desc, const int32_t* wg_start, 
 // replay) with the row index as the counter -- torch.rand over the 1.09 M rows of the lang-pretrain model cost 0.21 ms per step
 // plus two elementwise launches; this is one ~4 us launch.  Not torch's random stream: the reference's masks are not reproducible
 // across libraries either (parity fixtures run with drop_path = 0).
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
-
+// (philox4x32_10 itself lives in common.h: augment.hip draws its per-point noise from the same generator)
 __global__ void __launch_bounds__(256)
 k_row_keep_scales(const int64_t* __restrict__ seed, const float* __restrict__ keep, float* __restrict__ out, int64_t n) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;           // four consecutive rows per thread

@@ -92,7 +92,7 @@ def open_vocab_fragments(model, data_dict, text_embeddings, grid_size, chunk_siz
     return am, pred
 
 
-def _take_rows(t, idx32):
+def take_rows(t, idx32):
     """t[idx] for a per-point tensor: wide contiguous rows go through the library's row-gather kernel."""
     if t.dim() == 2 and t.is_contiguous() and (t.shape[1] * t.element_size()) % 16 == 0 and t.dtype in (torch.float32, torch.bfloat16, torch.float16):
         return nv.gather_rows(t, idx32)
@@ -138,7 +138,7 @@ def sphere_crop(data_dict, point_max=80000, sample_rate=None, mode="random", gen
         if isinstance(v, torch.Tensor):
             if v.shape[0] != n:
                 raise ValueError(f"sphere_crop: '{k}' has {v.shape[0]} rows, coord has {n}")
-            out[k] = _take_rows(v, idx)
+            out[k] = take_rows(v, idx)
     return out
 
 

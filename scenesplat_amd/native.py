@@ -895,6 +895,81 @@ def gather_add_rows(a, b, idx):
     return out
 
 
+# ---- per-sample Gaussian augmentations (csrc/augment.hip) -----------------------------------
+def _hf(values, count, name):
+    """A few host floats that travel as kernel arguments -> ctypes float array (None stays NULL)."""
+    if values is None:
+        return None
+    v = [float(x) for x in values]
+    if len(v) != count:
+        raise RuntimeError(f"{name}: expected {count} values, got {len(v)}")
+    return (ctypes.c_float * count)(*v)
+
+
+def _rows3(t, name, cols=3):
+    _req(t, torch.float32, name)
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise RuntimeError(f"{name}: expected (n, {cols}), got {tuple(t.shape)}")
+    return t
+
+
+def aug_bbox(x, affine=None):
+    """(6,) f32 device tensor {min xyz, max xyz} of x (n, 3), or of A x + b for affine = 12 host floats (A row-major, then b)."""
+    _rows3(x, "x")
+    n = x.shape[0]
+    if n < 1:
+        raise RuntimeError("aug_bbox: empty input")
+    part = torch.empty((lib().ss_aug_bbox_blocks(n), 6), dtype=torch.float32, device=x.device)
+    out = torch.empty(6, dtype=torch.float32, device=x.device)
+    check(lib().ss_aug_bbox(_p(x), n, _hf(affine, 12, "affine"), _p(part), _p(out), _stream()), "ss_aug_bbox")
+    return out
+
+
+def aug_gaussians_(coord=None, quat=None, scale=None, normal=None, affine=None, rquat=None, flip=0, scale_mul=None, lin=None,
+                   jitter=None, noise=None, seed=0):
+    """The fused rigid pass, in place (see include/scenesplat_hip.h).  jitter = (sigma, clip) or None; noise (n, 3) replays
+    recorded N(0,1) draws, otherwise the kernel draws them from `seed`."""
+    n = None
+    for t, name, cols in ((coord, "coord", 3), (quat, "quat", 4), (scale, "scale", 3), (normal, "normal", 3), (noise, "noise", 3)):
+        if t is None:
+            continue
+        _rows3(t, name, cols)
+        if n is not None and t.shape[0] != n:
+            raise RuntimeError(f"{name}: {t.shape[0]} rows, expected {n}")
+        n = t.shape[0]
+    if n is None:
+        return
+    sigma, clip = (0.0, 0.0) if jitter is None else (float(jitter[0]), float(jitter[1]))
+    check(lib().ss_aug_gaussians(_p(coord), _p(quat), _p(scale), _p(normal), n, _hf(affine, 12, "affine"), _hf(rquat, 4, "rquat"),
+                                 int(flip), _hf(scale_mul, 3, "scale_mul"), _hf(lin, 9, "lin"), int(jitter is not None), sigma, clip,
+                                 _p(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()), "ss_aug_gaussians")
+
+
+def aug_elastic_(coord, noise, origin, granularity, magnitude):
+    """coord += trilinear(noise (d0, d1, d2, 3), coord) * magnitude, in place; node i at origin + i * granularity."""
+    _rows3(coord, "coord"); _req(noise, torch.float32, "noise")
+    if noise.dim() != 4 or noise.shape[3] != 3:
+        raise RuntimeError(f"noise: expected (d0, d1, d2, 3), got {tuple(noise.shape)}")
+    d0, d1, d2 = noise.shape[:3]
+    check(lib().ss_aug_elastic(_p(coord), coord.shape[0], _p(noise), d0, d1, d2, _hf(origin, 3, "origin"), float(granularity),
+                               float(magnitude), _stream()), "ss_aug_elastic")
+
+
+AUG_COLOR_CONTRAST, AUG_COLOR_TRANSLATE, AUG_COLOR_JITTER = 1, 2, 4
+
+
+def aug_color_(color, flags=0, lo=None, hi=None, blend=0.0, tr=None, jitter_std=0.0, noise=None, seed=0, normalize=False):
+    """The colour steps on color (n, 3), 0..255, in place: contrast blend, translation + clip, jitter + clip, c / 127.5 - 1."""
+    _rows3(color, "color")
+    if noise is not None:
+        _rows3(noise, "noise")
+        if noise.shape[0] != color.shape[0]:
+            raise RuntimeError("noise: row count differs from color")
+    check(lib().ss_aug_color(_p(color), color.shape[0], int(flags), _hf(lo, 3, "lo"), _hf(hi, 3, "hi"), float(blend),
+                             _hf(tr, 3, "tr"), float(jitter_std), _p(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(normalize)),
+                             _stream()), "ss_aug_color")
+
+
 def segment_reduce(src, indices, idx_ptr, n_seg, mean):
     _req(src, None, "src"); _req(idx_ptr, torch.int32, "idx_ptr")
     if indices is not None:

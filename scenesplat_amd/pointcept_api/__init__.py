@@ -1,6 +1,6 @@
 """Host-side mirror of the pointcept interfaces the hot path sits behind (registries,
-``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, trainer/hook API)."""
-from .registry import HOOKS, LOSSES, MODELS, MODULES, TRAINERS, Registry, build_model  # noqa: F401
+``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, trainer/hook API, the training transforms)."""
+from .registry import HOOKS, LOSSES, MODELS, MODULES, TRAINERS, TRANSFORMS, Registry, build_model  # noqa: F401
 from .structure import Point  # noqa: F401
 from . import ptv3  # noqa: F401  (registers PT-v3m1)
 from . import lang  # noqa: F401  (registers LangPretrainer and the criteria)
@@ -9,3 +9,5 @@ from .lang import LangPretrainer, build_criteria  # noqa: F401
 from . import engine  # noqa: F401  (registers DefaultTrainer and the hooks)
 from . import seg  # noqa: F401  (registers DefaultSegmentorV2, CrossEntropyLoss, LovaszLoss, SemSegEvaluator)
 from .engine import HookBase, Trainer, TrainerBase, create_ddp_model  # noqa: F401
+from . import transform  # noqa: F401  (registers the per-sample training transforms)
+from .transform import Compose  # noqa: F401

@@ -78,6 +78,7 @@ MODULES = Registry("modules")
 LOSSES = Registry("losses")
 HOOKS = Registry("hooks")
 TRAINERS = Registry("trainers")
+TRANSFORMS = Registry("transforms")
 
 
 def build_model(cfg):
