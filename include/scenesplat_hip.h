@@ -109,6 +109,26 @@ int ss_grad_norm_finish(const double* partials, int num_partials, float max_norm
 int ss_adamw_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, const float* record,
                    ss_stream_t stream);
 
+/* ---- PDNorm prompt modulation of ALL PDNorm layers of a model, one grouped launch each way (csrc/pdnorm.hip; reference:
+ * pointcept/models/point_prompt_training/prompt_driven_normalization.py:8-53).  With s = silu(context) (context_channels fp32 values,
+ * silu(x) = x / (1 + exp(-x))) and [shift | scale] = W s + b per layer (W (2C, context_channels) row-major, b (2C)):
+ *   gamma_eff = gamma * (1 + scale),  beta_eff = beta * (1 + scale) + shift,  ops = 1 + scale      (gamma = 1 / beta = 0 where NULL).
+ * table: 14 int64 per layer {C, W, b, gamma | 0, beta | 0, gamma_eff, beta_eff, ops, dgamma_eff | 0, dbeta_eff | 0, dW, db,
+ * dgamma | 0, dbeta | 0}, all fp32 pointers; the forward reads words 0-7, the backward words 0-1, 3-4 and 7-13.  wg_start
+ * (num_layers + 1): first workgroup of each layer at ss_pdnorm_channels_per_workgroup() channels per workgroup.  vec4 != 0: 16-byte
+ * accesses; the caller guarantees context_channels % 4 == 0 and 16-byte aligned context, W and dW.
+ * Backward: d_shift = dbeta_eff, d_scale = dgamma_eff * gamma + dbeta_eff * beta, db = [d_shift | d_scale], dW = db (x) s,
+ * dgamma = dgamma_eff * ops, dbeta = dbeta_eff * ops, dcontext = silu'(context) * sum over layers of W^T db (a NULL dgamma_eff /
+ * dbeta_eff counts as zeros).  partials: total_workgroups * context_channels floats of scratch; the sum over workgroups is finished
+ * in a fixed order by a second small kernel: no atomics, bitwise reproducible.  split_workgroup in [0, total_workgroups]: the
+ * workgroups below it and from it on are summed apart and contribute silu' * A + silu' * B, bit for bit the sum of two calls over
+ * the two parts of the table (0 or total_workgroups: one part).  num_layers == 0: SS_OK without a launch. */
+int ss_pdnorm_channels_per_workgroup(void);
+int ss_pdnorm_mod_fwd(const int64_t* table, const int32_t* wg_start, int num_layers, int total_workgroups, const float* context,
+                      int context_channels, int vec4, ss_stream_t stream);
+int ss_pdnorm_mod_bwd(const int64_t* table, const int32_t* wg_start, int num_layers, int total_workgroups, const float* context,
+                      int context_channels, int vec4, int split_workgroup, float* partials, float* dcontext, ss_stream_t stream);
+
 /* ---- DropPath row scales (timm DropPath on (n, C) rows, ptv3:333-336) ------------------------------------
  * out[i] = Bernoulli(keep[i]) / keep[i] for the n rows of all residual seams of a forward; Philox4x32-10, counter = row index,
  * key = the 64-bit seed read from DEVICE memory (so a captured launch draws fresh masks per replay). */

@@ -51,6 +51,9 @@ PROTOTYPES = {
     "ss_grad_sqnorm_group": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "ss_grad_norm_finish": (c_i, [c_p, c_i, c_f, c_p, c_p]),
     "ss_adamw_group": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
+    "ss_pdnorm_channels_per_workgroup": (c_i, []),
+    "ss_pdnorm_mod_fwd": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p]),
+    "ss_pdnorm_mod_bwd": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "ss_linear_fwd_headmajor": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_f, c_p]),
     "ss_headmajor_pack": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_i, c_i, c_f, c_p]),
     "ss_window_attn_hm_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i, c_p, c_p, c_p]),

@@ -656,6 +656,7 @@ def bf16_of(p):
 # stay alive until its end (3 GB at dec0 for one chunk)
 WGRAD_GROUP_MAX_ROWS = int(os.environ.get("SS_WGRAD_GROUP_MAX", str(1 << 22)))    # 0 disables grouping
 _STAGE = {"cur": None, "route": {}}
+_UNFLUSHED = set()       # stages that hold queued LayerNorm partial sums (see _PDNormModulation.backward)
 
 
 # queued (x, dy) operands of a stage stay alive until its group is launched: 3 GB at dec0 for one 102,400-row chunk, 8x that for the
@@ -677,6 +678,7 @@ class _WgradStage:
             nv.linear_wgrad_group(q)
 
     def flush(self):
+        _UNFLUSHED.discard(self)
         q, self.queue, self.bytes = self.queue, [], 0
         r, self.redq = self.redq, []
         nv.linear_wgrad_group(q)
@@ -719,6 +721,7 @@ def reset_state():
     """Forget everything a forward pass leaves between its calls (the open stage, queued weight gradients, the remembered
     head sums): called after a forward / backward that ended in an exception, e.g. a refused hipGraph capture."""
     stage_end()
+    _UNFLUSHED.clear()
     _HEAD_CACHE.clear()
 
 
@@ -967,6 +970,7 @@ class _AddLayerNorm(torch.autograd.Function):
             if part is not None:
                 dst = torch.empty((2, part.shape[2]), dtype=torch.float32, device=part.device)
                 ctx.stage.redq.append((part, dst))
+                _UNFLUSHED.add(ctx.stage)
                 dg, db = dst[0], dst[1]
             return g_x, g_y, None, dg, db, None, None, None, None
         g_x, g_y, dg, db = nv.add_layernorm_bwd(g_xout, g_xcopy, g_h, xout, mean, rstd, g32, rowscale, x_dt, y_dt)
@@ -1000,9 +1004,17 @@ class _LnAddLn(torch.autograd.Function):
             g_x, g_t, part = nv.ln_add_ln_bwd(g_xout, g_h, xout, t, stats, g0, g1, x_dt, t_dt, reduce=False)
             dst = torch.empty((4, part.shape[2]), dtype=torch.float32, device=part.device)
             ctx.stage.redq.append((part, dst))
+            _UNFLUSHED.add(ctx.stage)
             return g_x, g_t, dst[0], dst[1], None, dst[2], dst[3], None, None, None
         g_x, g_t, dg0, db0, dg1, db1 = nv.ln_add_ln_bwd(g_xout, g_h, xout, t, stats, g0, g1, x_dt, t_dt)
         return g_x, g_t, dg0.to(p_dt), db0.to(p_dt), None, dg1.to(p_dt), db1.to(p_dt), None, None, None
+
+
+def _eff_stage(*ts):
+    """The open stage, for PDNorm's effective affine pairs (pdnorm_modulation's outputs): they are not parameters, so nothing is
+    routed, but the partial sums of their gradients ride in the stage's grouped reduction like those of the parameters they replace."""
+    cur = _STAGE["cur"]
+    return cur if cur is not None and all(getattr(t, "pdnorm_eff", False) for t in ts) else None
 
 
 def ln_add_ln(x, t, ln0, ln1, h_dtype=torch.float32):
@@ -1011,6 +1023,7 @@ def ln_add_ln(x, t, ln0, ln1, h_dtype=torch.float32):
     stage = s0 if (s0 is not None and s0 is s1 and s0 is s2 and s0 is s3) else None
     if stage is None:
         g0, b0, g1, b1 = ln0.weight, ln0.bias, ln1.weight, ln1.bias
+        stage = _eff_stage(g0, b0, g1, b1)
     return _LnAddLn.apply(x, t, g0, b0, ln0.eps, g1, b1, ln1.eps, h_dtype, stage)
 
 
@@ -1020,6 +1033,7 @@ def add_layer_norm(x, y, rowscale=None, gamma=None, beta=None, eps=1e-5, want_co
     stage = s0 if (s0 is not None and s0 is s1) else None
     if stage is None:
         ga, be = gamma, beta
+        stage = _eff_stage(ga, be) if ga is not None else None
     return _AddLayerNorm.apply(x, y, rowscale, ga, be, eps, want_copy, h_dtype, stage)
 
 
@@ -1069,3 +1083,70 @@ def batch_norm_act(x, bn, act=False):
     """x (n, C) through an nn.BatchNorm1d's parameters / buffers (updates running stats in training)."""
     return _BatchNormAct.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked if bn.training else None,
                                bn.training, bn.momentum, bn.eps, act)
+
+
+# ---- PDNorm prompt modulation: every PDNorm layer of a group in ONE launch each way (csrc/pdnorm.hip) ---------------------------
+class PDNormGroup:
+    """The PDNorm layers whose prompt arithmetic runs as one launch: rows = [(W, b, gamma | None, beta | None)] under ONE condition.
+    The descriptor table's fixed columns are built once and reused while the parameters stay where they are.  A group that is split
+    in two under a backward cut names the first row of its second part (split_row): its context gradient is then summed exactly
+    as the two groups' gradients add up, so the split backward reproduces the unsplit one bit for bit."""
+
+    def __init__(self, rows, split_row=0):
+        self.rows = [tuple(r) for r in rows]
+        self.split_row = int(split_row)      # rows from here on are the part that a split backward runs as a group of its own
+        self.tab = None
+
+    def table(self, context_channels):
+        if self.tab is None or self.tab.cc != context_channels or not self.tab.current(self.rows):
+            self.tab = nv.PDNormTable(self.rows, context_channels)
+        return self.tab
+
+
+class _PDNormModulation(torch.autograd.Function):
+    """(context, W_l, b_l, gamma_l, beta_l for every layer l) -> gamma_eff_0 .. gamma_eff_{L-1}, beta_eff_0 .. beta_eff_{L-1} as 2L
+    separate outputs: ONE node, whose backward runs once -- after the last norm of the backward pass has delivered its gradient."""
+
+    @staticmethod
+    def forward(ctx, group, context, *params):
+        c32 = context.detach().float().contiguous()
+        tab = group.table(c32.numel())
+        ctx.split_row = group.split_row
+        geff, beff, ops = nv.pdnorm_mod_fwd(c32, tab)
+        # the kernels read the parameters through the table's pointers: saved as well, so that autograd's version check sees an
+        # in-place update between forward and backward
+        ctx.save_for_backward(c32, ops, *[p for p in params if p is not None])
+        ctx.tab, ctx.context_meta = tab, (context.shape, context.dtype)
+        ctx.set_materialize_grads(False)
+        return tuple(geff) + tuple(beff)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        c32, ops = ctx.saved_tensors[:2]
+        n = len(grads) // 2
+        if all(g is None for g in grads):
+            return (None,) * (2 + 4 * n)
+        # LayerNorm seams hand over gradients whose partial sums their stage reduces in ONE grouped launch when the backward leaves the
+        # stage.  That has happened by now for every stage (this node was created before any of them, so it runs after their identity
+        # nodes); a stage that still holds sums is reduced here, before the gradients are read.
+        for st in list(_UNFLUSHED):
+            st.flush()
+        grads = [g.float().contiguous() if g is not None else None for g in grads]
+        dctx, dW, db, dg, dbt = nv.pdnorm_mod_bwd(c32, ctx.tab, ops, grads[:n], grads[n:], ctx.split_row)
+        shape, dtype = ctx.context_meta
+        out = [None, dctx.view(shape).to(dtype)]
+        for l in range(n):
+            out += [dW[l], db[l], dg[l], dbt[l]]
+        return tuple(out)
+
+
+def pdnorm_modulation(group, context):
+    """-> [(gamma_eff, beta_eff)] of every layer of the group for this context (1, context_channels)."""
+    if not (torch.is_tensor(context) and context.is_cuda):
+        raise RuntimeError("pdnorm_modulation: context must be a GPU tensor (no CPU fallback)")
+    flat = [t for r in group.rows for t in r]
+    outs = _PDNormModulation.apply(group, context, *flat)
+    for o in outs:
+        o.pdnorm_eff = True            # (read by _eff_stage)
+    n = len(group.rows)
+    return list(zip(outs[:n], outs[n:]))

@@ -1293,3 +1293,115 @@ def adamw_group(rows, record=None):
     desc[:, 6:].view(np.float32)[:, :7] = np.asarray([r[4] for r in rows], dtype=np.float64)   # fp32 over the last four words
     d_dev, s_dev = _upload_descriptors(desc, starts, dev)
     check(lib().ss_adamw_group(_p(d_dev), _p(s_dev), n, starts[-1], _p(record), _stream()), "ss_adamw_group")
+
+
+# ---- PDNorm prompt modulation of all PDNorm layers of a model: one grouped launch each way (csrc/pdnorm.hip) --------------------
+PDNORM_WORDS = 14
+
+
+class PDNormTable:
+    """Host side of the descriptor table of a group of PDNorm layers under ONE condition: the columns that do not change from call
+    to call (C, W, b, gamma, beta), built once and reused while the parameters stay where they are (`current`)."""
+
+    def __init__(self, rows, context_channels):
+        import numpy as np
+        if not rows:
+            raise RuntimeError("pdnorm: an empty group has no table")
+        self.cc = int(context_channels)
+        self.dev = _req(rows[0][0], torch.float32, "rows[0].W").device
+        self.widths = []
+        for j, (w, b, g, be) in enumerate(rows):
+            if w.dim() != 2 or w.shape[0] % 2 or w.shape[1] != self.cc:
+                raise RuntimeError(f"rows[{j}].W: expected (2C, {self.cc}), got {tuple(w.shape)}")
+            c = w.shape[0] // 2
+            _optim_check(w, 2 * c * self.cc, self.dev, f"rows[{j}].W")
+            _optim_check(b, 2 * c, self.dev, f"rows[{j}].b")
+            for t, nm in ((g, "gamma"), (be, "beta")):
+                if t is not None:
+                    _optim_check(t, c, self.dev, f"rows[{j}].{nm}")
+            self.widths.append(c)
+        per = lib().ss_pdnorm_channels_per_workgroup()
+        self.starts = [0]
+        for c in self.widths:
+            self.starts.append(self.starts[-1] + (c + per - 1) // per)
+        self.sig = self.signature(rows)
+        self.desc = np.zeros((len(rows), PDNORM_WORDS), dtype=np.int64)
+        self.desc[:, 0] = self.widths
+        self.desc[:, 1:5] = np.asarray(self.sig, dtype=np.int64).reshape(len(rows), 4)
+        self.off = np.concatenate([[0], np.cumsum(self.widths)]).astype(np.int64)          # channel offsets of the layers
+        self.w_off = np.concatenate([[0], np.cumsum([2 * c * self.cc for c in self.widths])]).astype(np.int64)
+        self.vec4 = int(self.cc % 4 == 0 and not np.any(self.desc[:, 1] & 15))
+        self.affine = [(g is not None, be is not None) for _, _, g, be in rows]
+
+    @staticmethod
+    def signature(rows):
+        return tuple(t.data_ptr() if t is not None else 0 for r in rows for t in r)
+
+    def current(self, rows):
+        return self.signature(rows) == self.sig
+
+
+def _pdnorm_context(context, tab):
+    _req(context, torch.float32, "context")
+    if context.numel() != tab.cc or context.device != tab.dev:
+        raise RuntimeError(f"context: expected {tab.cc} values on {tab.dev} (one prompt per batch)")
+    return context
+
+
+def pdnorm_mod_fwd(context, tab):
+    """-> (gamma_eff list, beta_eff list, ops): the folded affine pair of every layer of the table and 1 + scale (all channels of all
+    layers in one tensor, for the backward).  ONE launch; the outputs are separate views of one allocation."""
+    _pdnorm_context(context, tab)
+    total = int(tab.off[-1])
+    out = torch.empty(3 * total, dtype=torch.float32, device=tab.dev)
+    desc = tab.desc.copy()
+    base = out.data_ptr()
+    desc[:, 5] = base + 4 * tab.off[:-1]
+    desc[:, 6] = base + 4 * (total + tab.off[:-1])
+    desc[:, 7] = base + 4 * (2 * total + tab.off[:-1])
+    d_dev, s_dev = _upload_descriptors(desc, tab.starts, tab.dev)
+    vec4 = int(tab.vec4 and context.data_ptr() % 16 == 0)
+    check(lib().ss_pdnorm_mod_fwd(_p(d_dev), _p(s_dev), len(tab.widths), tab.starts[-1], _p(context), tab.cc, vec4, _stream()),
+          "ss_pdnorm_mod_fwd")
+    o = [int(x) for x in tab.off]
+    geff = [out[o[l]:o[l + 1]] for l in range(len(tab.widths))]
+    beff = [out[total + o[l]:total + o[l + 1]] for l in range(len(tab.widths))]
+    return geff, beff, out[2 * total:]
+
+
+def pdnorm_mod_bwd(context, tab, ops, dgeff, dbeff, split_row=0):
+    """Backward of pdnorm_mod_fwd from the gradients the norm kernels returned for gamma_eff / beta_eff (None: that norm sent none).
+    -> (dcontext (context's shape), dW list, db list, dgamma list, dbeta list); dgamma / dbeta are None for affine-free rows.
+    ONE grouped launch plus the fixed-order finish of dcontext.  split_row: the rows below it and from it on contribute to dcontext
+    as two launches over the two parts would (bit for bit): the unsplit form of a backward that may also run in two calls."""
+    _pdnorm_context(context, tab)
+    n = len(tab.widths)
+    total = int(tab.off[-1])
+    _optim_check(ops, total, tab.dev, "ops")
+    for l in range(n):
+        for t, nm in ((dgeff[l], "dgamma_eff"), (dbeff[l], "dbeta_eff")):
+            if t is not None:
+                _optim_check(t, tab.widths[l], tab.dev, f"{nm}[{l}]")
+    wtot = int(tab.w_off[-1])
+    out = torch.empty(wtot + 4 * total, dtype=torch.float32, device=tab.dev)      # dW | db (2 per channel) | dgamma | dbeta
+    partials = torch.empty(tab.starts[-1] * tab.cc, dtype=torch.float32, device=tab.dev)
+    dcontext = torch.empty_like(context)
+    desc = tab.desc.copy()
+    base = out.data_ptr()
+    desc[:, 7] = ops.data_ptr() + 4 * tab.off[:-1]
+    desc[:, 8] = [t.data_ptr() if t is not None else 0 for t in dgeff]
+    desc[:, 9] = [t.data_ptr() if t is not None else 0 for t in dbeff]
+    desc[:, 10] = base + 4 * tab.w_off[:-1]
+    desc[:, 11] = base + 4 * (wtot + 2 * tab.off[:-1])
+    desc[:, 12] = [base + 4 * (wtot + 2 * total + int(tab.off[l])) if tab.affine[l][0] else 0 for l in range(n)]
+    desc[:, 13] = [base + 4 * (wtot + 3 * total + int(tab.off[l])) if tab.affine[l][1] else 0 for l in range(n)]
+    d_dev, s_dev = _upload_descriptors(desc, tab.starts, tab.dev)
+    vec4 = int(tab.vec4 and context.data_ptr() % 16 == 0 and base % 16 == 0)
+    check(lib().ss_pdnorm_mod_bwd(_p(d_dev), _p(s_dev), n, tab.starts[-1], _p(context), tab.cc, vec4, int(tab.starts[split_row]), _p(partials), _p(dcontext),
+                                  _stream()), "ss_pdnorm_mod_bwd")
+    o, wo = [int(x) for x in tab.off], [int(x) for x in tab.w_off]
+    dW = [out[wo[l]:wo[l + 1]].view(2 * tab.widths[l], tab.cc) for l in range(n)]
+    db = [out[wtot + 2 * o[l]:wtot + 2 * o[l + 1]] for l in range(n)]
+    dg = [out[wtot + 2 * total + o[l]:wtot + 2 * total + o[l + 1]] if tab.affine[l][0] else None for l in range(n)]
+    dbt = [out[wtot + 3 * total + o[l]:wtot + 3 * total + o[l + 1]] if tab.affine[l][1] else None for l in range(n)]
+    return dcontext, dW, db, dg, dbt

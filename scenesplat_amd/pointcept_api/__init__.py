@@ -1,5 +1,5 @@
 """Host-side mirror of the pointcept interfaces the hot path sits behind (registries,
-``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, trainer/hook API, the training transforms)."""
+``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, ``PDNorm`` / ``PPT-v1m2``, trainer/hook API, the training transforms)."""
 from .registry import HOOKS, LOSSES, MODELS, MODULES, TRAINERS, TRANSFORMS, Registry, build_model  # noqa: F401
 from .structure import Point  # noqa: F401
 from . import ptv3  # noqa: F401  (registers PT-v3m1)
@@ -11,3 +11,5 @@ from . import seg  # noqa: F401  (registers DefaultSegmentorV2, CrossEntropyLoss
 from .engine import HookBase, Trainer, TrainerBase, create_ddp_model  # noqa: F401
 from . import transform  # noqa: F401  (registers the per-sample training transforms)
 from .transform import Compose  # noqa: F401
+from . import ppt  # noqa: F401  (registers PPT-v1m2)
+from .pdnorm import PDNorm  # noqa: F401  (registered in MODULES)

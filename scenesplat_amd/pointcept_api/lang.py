@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 from .. import functional as SF
 from .. import native as nv
+from .pdnorm import condition_key
 from .registry import LOSSES, MODELS, build_model
 from .structure import Point
 
@@ -185,7 +186,8 @@ class LangPretrainer(nn.Module):
                 gates.append(bool(ep > (1 - c.last_percent)))
             else:
                 gates.append(sched)
-        return tuple(gates)
+        # a backbone with PDNorm layers bakes the selected norms into a captured step: the condition's index belongs to the key
+        return tuple(gates) + condition_key(self.backbone, host)
 
     def forward(self, input_dict, chunk_size=None):
         if chunk_size is not None and chunk_size > 0 and input_dict["coord"].shape[0] > chunk_size:

@@ -17,6 +17,7 @@ were trained with:
   * tail windows are topped up with points borrowed from the previous window (ptv3:145-154).
 """
 import os
+from functools import partial
 
 import torch
 import torch.nn as nn
@@ -25,6 +26,7 @@ import torch.nn.functional as F
 from .. import functional as SF
 from .. import native as nv
 from ..plan import build_plan
+from .pdnorm import PDNorm, PointModule, ResolvedNorm, pdnorm_layers, resolved as _rn
 from .registry import MODELS
 from .structure import Point
 
@@ -65,10 +67,6 @@ def conv_dtype_for(out_channels):
     if cd == torch.bfloat16 and out_channels <= RUNTIME.get("conv_split_max_channels", 0):
         return "bf16x3"
     return cd
-
-
-class PointModule(nn.Module):
-    """Marker base class, as pointcept/models/modules.py:8-14."""
 
 
 class DropPath(nn.Module):
@@ -226,7 +224,7 @@ class Block(PointModule):
         if not self.pre_norm:
             return self._forward_post_norm(x, conv_in, level), None
         hdt = torch.bfloat16 if torch.is_autocast_enabled() else torch.float32
-        ln0, ln1, ln2 = self.cpe[2], self.norm1[0], self.norm2[0]
+        ln0, ln1, ln2 = _rn(self.cpe[2]), _rn(self.norm1[0]), _rn(self.norm2[0])      # PDNorm layers: as resolved for this forward
         t = _lin(self.cpe[1], self.cpe[0](conv_in, level))
         if RUNTIME.get("fuse_ln_seam", True) and x.shape[1] % 4 == 0 and x.shape[1] <= 1024:
             x, h = SF.ln_add_ln(x, t, ln0, ln1, hdt)           # x += LN0(t); h = LN1(x): one pass
@@ -258,7 +256,9 @@ class Block(PointModule):
 
 def _norm_act(x, norm, act):
     """BatchNorm1d (+ GELU) as one fused HIP op (csrc/norm.hip); anything else falls through to the modules."""
-    if isinstance(norm, nn.BatchNorm1d) and norm.affine and norm.track_running_stats and (act is None or isinstance(act, nn.GELU)) \
+    norm = _rn(norm)
+    if (isinstance(norm, nn.BatchNorm1d) or getattr(norm, "is_bn", False)) and norm.affine and norm.track_running_stats \
+            and (act is None or isinstance(act, nn.GELU)) \
             and x.shape[1] % 4 == 0 and x.shape[1] <= 1024:
         return SF.batch_norm_act(x, norm, act is not None)
     if norm is not None:
@@ -268,9 +268,9 @@ def _norm_act(x, norm, act):
 
 def _seq_lin_norm_act(seq, x):
     """nn.Sequential(Linear[, BatchNorm1d][, GELU]) with the norm/act pair fused."""
-    mods = list(seq)
+    mods = [_rn(m) for m in seq]
     x = _lin(mods[0], x) if isinstance(mods[0], nn.Linear) else mods[0](x)
-    norm = mods[1] if len(mods) > 1 and isinstance(mods[1], nn.BatchNorm1d) else None
+    norm = mods[1] if len(mods) > 1 and (isinstance(mods[1], nn.BatchNorm1d) or getattr(mods[1], "is_bn", False)) else None
     act = mods[-1] if len(mods) > 1 and isinstance(mods[-1], nn.GELU) else None
     if norm is None and act is None:
         for mod in mods[1:]:
@@ -371,8 +371,9 @@ class PointTransformerV3(PointModule):
                  pdnorm_bn=False, pdnorm_ln=False, pdnorm_decouple=True, pdnorm_adaptive=False, pdnorm_affine=True,
                  pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D")):
         super().__init__()
-        if pdnorm_bn or pdnorm_ln:
-            raise NotImplementedError("PDNorm is off in every SceneSplat language config; not on the HIP path")
+        if (pdnorm_bn or pdnorm_ln) and not pdnorm_decouple:
+            raise ValueError("pdnorm_decouple=False cannot run in the reference (PDNorm keeps the un-called norm_layer factory and calls "
+                             "it on the features): refused instead of inventing semantics")
         self.num_stages = len(enc_depths)
         self.order = [order] if isinstance(order, str) else list(order)
         self.cls_mode, self.shuffle_orders = cls_mode, shuffle_orders
@@ -381,10 +382,17 @@ class PointTransformerV3(PointModule):
         assert cls_mode or self.num_stages == len(dec_depths) + 1 == len(dec_channels) + 1
         assert cls_mode or self.num_stages == len(dec_num_head) + 1 == len(dec_patch_size) + 1
 
-        def bn_layer(c):
-            return nn.BatchNorm1d(c, eps=1e-3, momentum=0.01)
-
-        ln_layer, act_layer = nn.LayerNorm, nn.GELU
+        # norm layers, as ptv3:570-591: PDNorm keeps one norm per condition (and, adaptive, a prompt-driven scale / shift)
+        pdn = dict(conditions=pdnorm_conditions, decouple=pdnorm_decouple, adaptive=pdnorm_adaptive)
+        if pdnorm_bn:
+            bn_layer = partial(PDNorm, norm_layer=partial(nn.BatchNorm1d, eps=1e-3, momentum=0.01, affine=pdnorm_affine), **pdn)
+        else:
+            bn_layer = partial(nn.BatchNorm1d, eps=1e-3, momentum=0.01)
+        if pdnorm_ln:
+            ln_layer = partial(PDNorm, norm_layer=partial(nn.LayerNorm, elementwise_affine=pdnorm_affine), **pdn)
+        else:
+            ln_layer = nn.LayerNorm
+        act_layer = nn.GELU
         self.enc_channels = tuple(enc_channels)
         self.dec_channels_ = tuple(dec_channels) if not cls_mode else ()        # width of the decoder stage at level s
         self.embedding = Embedding(in_channels, enc_channels[0], bn_layer, act_layer)
@@ -480,7 +488,8 @@ class PointTransformerV3(PointModule):
         cache = self.__dict__.setdefault("_stage_linear_cache", {})
         ls = cache.get(id(stage))
         if ls is None:
-            ls = [m for m in stage.modules() if isinstance(m, (nn.Linear, nn.LayerNorm))]
+            skip = self._modulation_linears()       # (PDNorm's prompt Linears run in the grouped modulation launch, not through SF.linear)
+            ls = [m for m in stage.modules() if isinstance(m, (nn.Linear, nn.LayerNorm)) and id(m) not in skip]
             cache[id(stage)] = ls
         return ls
 
@@ -488,9 +497,9 @@ class PointTransformerV3(PointModule):
         """bf16 copies of every Linear / SubMConv3d weight and Linear bias, refreshed with multi-tensor copies."""
         ps = self.__dict__.get("_shadow_lists")
         if ps is None or ps[2] != next(self.parameters()).device:
-            params = []
+            params, skip = [], self._modulation_linears()
             for m in self.modules():
-                if isinstance(m, nn.Linear):
+                if isinstance(m, nn.Linear) and id(m) not in skip:
                     params += [m.weight, m.bias]
                 elif isinstance(m, SubMConv3d):
                     params += [m.weight, m.bias]         # (the bias feeds the small levels' im2col GEMM as a bf16 operand)
@@ -512,6 +521,45 @@ class PointTransformerV3(PointModule):
         SF.refresh_shadows(ps[0], ps[1])
         if torch.is_grad_enabled():
             nv.zero_arena_begin(ps[3], ps[2])
+
+    def _pdnorm(self):
+        pds = self.__dict__.get("_pdnorm_list")
+        if pds is None:
+            pds = self.__dict__["_pdnorm_list"] = pdnorm_layers(self)
+        return pds
+
+    def _modulation_linears(self):
+        return {id(m.modulation[1]) for m in self._pdnorm() if m.adaptive}
+
+    def _resolve_pdnorm(self, point):
+        """Select the batch's condition in every PDNorm layer, once per forward: each layer resolves to (gamma_eff, beta_eff, eps and
+        the selected norm's buffers) for the call sites (pdnorm.resolved).  Without `adaptive` that is the selected module's own
+        parameters.  With it, the prompt arithmetic of all layers is ONE grouped launch (SF.pdnorm_modulation) -- two under a
+        backward cut, where the backward runs as two autograd calls and one node would be entered twice: the layers of the last
+        decoder stage form a group of their own.  Both groups send their gradient to `context`; the single group sums its context
+        gradient in the same two parts, so the split backward gives the unsplit one's gradient bit for bit."""
+        pds = self._pdnorm()
+        assert "condition" in point.keys(), f"feat and condition must be in point.keys(): {point.keys()}"
+        idx = pds[0].index_of(point["condition"])
+        if not pds[0].adaptive:
+            for m in pds:
+                m.__dict__["_resolved"] = m.resolve_static(idx)
+            return
+        assert "context" in point.keys()
+        split = (not self.cls_mode and torch.is_grad_enabled() and point.get("backward_cut", None) is not None)
+        cache = self.__dict__.setdefault("_pdnorm_groups", {})
+        groups = cache.get((idx, split))
+        if groups is None:
+            last = {id(m) for m in pdnorm_layers(self.dec.dec0)} if not self.cls_mode else set()
+            parts = [[m for m in pds if id(m) not in last], [m for m in pds if id(m) in last]]
+            if not split:        # one group, the last decoder stage's rows at its end: summed as the two groups would be
+                parts = [(parts[0] + parts[1], len(parts[0]))]
+            else:
+                parts = [(ms, 0) for ms in parts if ms]
+            groups = cache[(idx, split)] = [(ms, SF.PDNormGroup([m.row(idx) for m in ms], sp)) for ms, sp in parts]
+        for ms, group in groups:
+            for m, (g, b) in zip(ms, SF.pdnorm_modulation(group, point["context"])):
+                m.__dict__["_resolved"] = ResolvedNorm(g, b, m.norm[idx])
 
     def _draw_row_scales(self, levels, device):
         """DropPath masks (one Bernoulli(keep)/keep scale per row and residual seam, timm DropPath on (n,C) rows as
@@ -577,6 +625,17 @@ class PointTransformerV3(PointModule):
         levels = plan.levels
         if self.training:
             self._draw_row_scales(levels, feat.device)
+        if self._pdnorm():
+            self._resolve_pdnorm(point)
+            try:
+                return self._forward_levels(point, feat, plan)
+            finally:
+                for m in self._pdnorm():              # (the resolved pairs belong to this forward's autograd graph)
+                    m.__dict__.pop("_resolved", None)
+        return self._forward_levels(point, feat, plan)
+
+    def _forward_levels(self, point, feat, plan):
+        levels = plan.levels
         x = self.embedding(feat, levels[0])
         skips = []
         for s in range(self.num_stages):

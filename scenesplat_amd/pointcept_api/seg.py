@@ -20,6 +20,7 @@ from .. import native as nv
 from .. import pointops
 from .engine import HookBase, get_world_size, is_main_process
 from .lang import build_criteria
+from .pdnorm import condition_key
 from .registry import HOOKS, LOSSES, MODELS, build_model
 from .structure import Point
 
@@ -175,7 +176,7 @@ class DefaultSegmentorV2(nn.Module):
 
     def steady_key(self, host):
         """No host-side decision depends on the step's host values (the steady-state replay keys on this, not on epoch_progress)."""
-        return ()
+        return condition_key(self.backbone, host)        # (a backbone with PDNorm layers: the selected norms are baked into a capture)
 
     def forward(self, input_dict):
         point = self.backbone(Point(input_dict))
