@@ -309,6 +309,27 @@ int ss_ln_add_ln_bwd(const float* g_xout, const void* g_h, int g_h_dtype, const 
                      const float* stats, const float* gamma0, const float* gamma1, void* g_x, int g_x_dtype, void* g_t,
                      int g_t_dtype, float* part, int64_t n, int channels, int nblocks, ss_stream_t stream);
 int ss_add_layernorm_bwd_blocks(int64_t n);
+
+/* ---- fused tail of a pre-norm Block at C in {32, 64, 128, 256}, hidden = 4C (ptv3:318-338): proj + residual + LN2 + fc1 + GELU +
+ * fc2 + residual in ONE launch each way.  feat (n, C) bf16 = attention output, x (n, C) f32 = residual stream, rs1 / rs2 (n) f32
+ * DropPath row scales or NULL; wp (C, C), w1 (4C, C), w2 (C, 4C) bf16 row-major; gamma / beta f32; the three biases all f32 or all
+ * bf16 (bias_dtype SS_DTYPE_F32 | SS_DTYPE_BF16: the bf16 shadows today's GEMMs read), added in fp32 to the fp32 accumulator.
+ *   y1 = bf16(feat wp^T + bp); x_mid = x + rs1 y1; h2 = bf16(LN(x_mid) gamma + beta); u = bf16(h2 w1^T + b1); a = bf16(gelu(u));
+ *   y2 = bf16(a w2^T + b2); x_out = x_mid + rs2 y2 [+ bf16 copy, NULL = none].  Written: x_mid, mean, rstd, h2, u, a, x_out.
+ * Backward: g = g_xout (+ g_xcopy); dy2 = bf16(rs2 g); da = bf16(dy2 w2); du = bf16(da gelu'(u)); dh2 = bf16(du w1);
+ *   g_mid = g + LN'(dh2); dy1 = bf16(rs1 g_mid); dfeat = bf16(dy1 wp).  wp_t / w1_t / w2_t are the (in, out) copies of the weights.
+ *   part (2, nblocks, C) f32 = per-workgroup partial sums of dgamma, dbeta with nblocks = ss_block_tail_bwd_blocks(n); no atomics.
+ * One workgroup owns ss_block_tail_rows() rows.  Every tensor 16-byte aligned. */
+int ss_block_tail_rows(void);
+int ss_block_tail_bwd_blocks(int64_t n);
+int ss_block_tail_fwd(const void* feat, const float* x, const float* rs1, const float* rs2, const void* wp, const void* bp,
+                      const void* w1, const void* b1, const void* w2, const void* b2, int bias_dtype, const float* gamma, const float* beta,
+                      float eps, float* x_mid, float* mean, float* rstd, void* h2, void* u, void* a, float* x_out,
+                      void* xcopy_bf16, int64_t n, int channels, ss_stream_t stream);
+int ss_block_tail_bwd(const float* g_xout, const void* g_xcopy_bf16, const float* x_mid, const float* mean, const float* rstd,
+                      const void* u, const float* rs1, const float* rs2, const float* gamma, const void* wp_t, const void* w1_t,
+                      const void* w2_t, float* g_mid, void* dfeat, void* dy2, void* du, void* dy1, float* part, int64_t n,
+                      int channels, int nblocks, ss_stream_t stream);
 /* ONE launch reducing many partial-sum blocks (the dgamma / dbeta partials of a whole stage): desc (nprob, 4) int64 device =
  * {part (K, nb, C) f32, dst (K*C) f32, nb, C | (K*C) << 32}; wg_start (nprob + 1) int32 device, problem p owns
  * ceil(K*C / 256) workgroups; dst[k*C + c] = sum_b part[k][b][c]. */

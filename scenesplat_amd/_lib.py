@@ -101,6 +101,10 @@ PROTOTYPES = {
     "ss_subm_f32_wgrad": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),
     "ss_add_layernorm_fwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i64, c_i, c_p]),
     "ss_add_layernorm_bwd_blocks": (c_i, [c_i64]),
+    "ss_block_tail_rows": (c_i, []),
+    "ss_block_tail_bwd_blocks": (c_i, [c_i64]),
+    "ss_block_tail_fwd": (c_i, [c_p] * 10 + [c_i, c_p, c_p, c_f] + [c_p] * 8 + [c_i64, c_i, c_p]),
+    "ss_block_tail_bwd": (c_i, [c_p] * 18 + [c_i64, c_i, c_i, c_p]),
     "ss_group_partial_sums_outputs_per_workgroup": (c_i, []),
     "ss_group_partial_sums": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "ss_transpose16_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),

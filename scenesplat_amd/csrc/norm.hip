@@ -9,22 +9,12 @@
 // One wave per row, 4 elements per lane per step (16-byte fp32 / 8-byte bf16 accesses, fully
 // coalesced 1 KiB / 512 B per wave instruction); the row lives in registers between the two passes.
 #include "common.h"
+#include "rowmath.h"
 #include "../../include/scenesplat_hip.h"
 
 #define LN_THREADS 256
 #define LN_MAXIT 4   // C <= 1024
 
-__device__ __forceinline__ float4 ln_ld4(const void* p, int dtype, int64_t idx) {
-  if (dtype == SS_F32) return *reinterpret_cast<const float4*>((const float*)p + idx);
-  uint2 u = *reinterpret_cast<const uint2*>((const unsigned short*)p + idx);
-  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                     __uint_as_float(u.y & 0xffff0000u));
-}
-__device__ __forceinline__ void ln_st4(void* p, int dtype, int64_t idx, float4 v) {
-  if (dtype == SS_F32) { *reinterpret_cast<float4*>((float*)p + idx) = v; return; }
-  uint2 u; u.x = pack_bf16x2(v.x, v.y); u.y = pack_bf16x2(v.z, v.w);
-  *reinterpret_cast<uint2*>((unsigned short*)p + idx) = u;
-}
 
 template <int IT>
 __global__ void __launch_bounds__(LN_THREADS)
@@ -48,7 +38,7 @@ k_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ y, i
       v[i] = a;
       if (xout) ln_st4(xout, xout_dt, row * C + j, a);
       if (xcopy) ln_st4(xcopy, SS_BF16, row * C + j, a);
-      sum += a.x + a.y + a.z + a.w;
+      sum += ln_sum4(a);
     }
   }
   if (!gamma) return;
@@ -57,10 +47,7 @@ k_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ y, i
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     int j = i * 256 + lane * 4;
-    if (j < C) {
-      float dx = v[i].x - mu, dy = v[i].y - mu, dz = v[i].z - mu, dw = v[i].w - mu;
-      sq += dx * dx + dy * dy + dz * dz + dw * dw;
-    }
+    if (j < C) sq += ln_sqdev4(v[i], mu);
   }
   const float r = rsqrtf(wave_reduce_sum(sq) / C + eps);
   if (lane == 0) { mean[row] = mu; rstd[row] = r; }
@@ -69,9 +56,7 @@ k_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ y, i
     int j = i * 256 + lane * 4;
     if (j < C) {
       float4 g = *reinterpret_cast<const float4*>(gamma + j), b = *reinterpret_cast<const float4*>(beta + j);
-      float4 o = make_float4((v[i].x - mu) * r * g.x + b.x, (v[i].y - mu) * r * g.y + b.y, (v[i].z - mu) * r * g.z + b.z,
-                             (v[i].w - mu) * r * g.w + b.w);
-      ln_st4(h, h_dt, row * C + j, o);
+      ln_st4(h, h_dt, row * C + j, ln_apply4(v[i], mu, r, g, b));
     }
   }
 }
@@ -107,9 +92,9 @@ k_add_ln_bwd(const void* __restrict__ g_xout, int gxo_dt, const void* __restrict
         xh[i] = make_float4(0.f, 0.f, 0.f, 0.f); gy[i] = xh[i];
         if (j < C) {
           float4 a = ln_ld4(v_in, v_dt, row * C + j), g = ln_ld4(g_h, gh_dt, row * C + j);
-          xh[i] = make_float4((a.x - mu) * r, (a.y - mu) * r, (a.z - mu) * r, (a.w - mu) * r);
+          xh[i] = ln_xhat4(a, mu, r);
           gy[i] = make_float4(g.x * gm[i].x, g.y * gm[i].y, g.z * gm[i].z, g.w * gm[i].w);
-          c1 += gy[i].x + gy[i].y + gy[i].z + gy[i].w;
+          c1 += ln_sum4(gy[i]);
           c2 += gy[i].x * xh[i].x + gy[i].y * xh[i].y + gy[i].z * xh[i].z + gy[i].w * xh[i].w;
           dg[i].x += g.x * xh[i].x; dg[i].y += g.y * xh[i].y; dg[i].z += g.z * xh[i].z; dg[i].w += g.w * xh[i].w;
           db[i].x += g.x; db[i].y += g.y; db[i].z += g.z; db[i].w += g.w;
@@ -118,8 +103,7 @@ k_add_ln_bwd(const void* __restrict__ g_xout, int gxo_dt, const void* __restrict
       c1 = wave_reduce_sum(c1) / C; c2 = wave_reduce_sum(c2) / C;
 #pragma unroll
       for (int i = 0; i < IT; ++i)
-        gv[i] = make_float4(r * (gy[i].x - c1 - xh[i].x * c2), r * (gy[i].y - c1 - xh[i].y * c2),
-                            r * (gy[i].z - c1 - xh[i].z * c2), r * (gy[i].w - c1 - xh[i].w * c2));
+        gv[i] = ln_dx4(gy[i], xh[i], c1, c2, r);
     } else {
 #pragma unroll
       for (int i = 0; i < IT; ++i) gv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -225,14 +209,14 @@ k_ln_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ t
   for (int i = 0; i < IT; ++i) {
     int j = i * 256 + lane * 4;
     v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j < C) { v[i] = ln_ld4(t, t_dt, row * C + j); sum += v[i].x + v[i].y + v[i].z + v[i].w; }
+    if (j < C) { v[i] = ln_ld4(t, t_dt, row * C + j); sum += ln_sum4(v[i]); }
   }
   const float mu0 = wave_reduce_sum(sum) / C;
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     int j = i * 256 + lane * 4;
-    if (j < C) { float a = v[i].x - mu0, b = v[i].y - mu0, c = v[i].z - mu0, d = v[i].w - mu0; sq += a * a + b * b + c * c + d * d; }
+    if (j < C) sq += ln_sqdev4(v[i], mu0);
   }
   const float r0 = rsqrtf(wave_reduce_sum(sq) / C + eps0);
   sum = 0.f;
@@ -246,7 +230,7 @@ k_ln_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ t
       a.z += (v[i].z - mu0) * r0 * g.z + b.z; a.w += (v[i].w - mu0) * r0 * g.w + b.w;
       v[i] = a;
       *reinterpret_cast<float4*>(xout + row * C + j) = a;
-      sum += a.x + a.y + a.z + a.w;
+      sum += ln_sum4(a);
     }
   }
   const float mu1 = wave_reduce_sum(sum) / C;
@@ -254,7 +238,7 @@ k_ln_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ t
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     int j = i * 256 + lane * 4;
-    if (j < C) { float a = v[i].x - mu1, b = v[i].y - mu1, c = v[i].z - mu1, d = v[i].w - mu1; sq += a * a + b * b + c * c + d * d; }
+    if (j < C) sq += ln_sqdev4(v[i], mu1);
   }
   const float r1 = rsqrtf(wave_reduce_sum(sq) / C + eps1);
   if (lane == 0) *reinterpret_cast<float4*>(stats + row * 4) = make_float4(mu0, r0, mu1, r1);
@@ -263,8 +247,7 @@ k_ln_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ t
     int j = i * 256 + lane * 4;
     if (j < C) {
       float4 g = *reinterpret_cast<const float4*>(gamma1 + j), b = *reinterpret_cast<const float4*>(beta1 + j);
-      ln_st4(h, h_dt, row * C + j, make_float4((v[i].x - mu1) * r1 * g.x + b.x, (v[i].y - mu1) * r1 * g.y + b.y,
-                                               (v[i].z - mu1) * r1 * g.z + b.z, (v[i].w - mu1) * r1 * g.w + b.w));
+      ln_st4(h, h_dt, row * C + j, ln_apply4(v[i], mu1, r1, g, b));
     }
   }
 }
@@ -274,13 +257,11 @@ k_ln_add_ln_fwd(const void* __restrict__ x, int x_dt, const void* __restrict__ t
   {                                                                                                       \
     float c1_ = 0.f, c2_ = 0.f;                                                                           \
     _Pragma("unroll") for (int i = 0; i < IT; ++i) {                                                      \
-      c1_ += GY[i].x + GY[i].y + GY[i].z + GY[i].w;                                                       \
+      c1_ += ln_sum4(GY[i]);                                                                              \
       c2_ += GY[i].x * XH[i].x + GY[i].y * XH[i].y + GY[i].z * XH[i].z + GY[i].w * XH[i].w;               \
     }                                                                                                     \
     c1_ = wave_reduce_sum(c1_) / C; c2_ = wave_reduce_sum(c2_) / C;                                       \
-    _Pragma("unroll") for (int i = 0; i < IT; ++i)                                                        \
-      OUT[i] = make_float4(R * (GY[i].x - c1_ - XH[i].x * c2_), R * (GY[i].y - c1_ - XH[i].y * c2_),      \
-                           R * (GY[i].z - c1_ - XH[i].z * c2_), R * (GY[i].w - c1_ - XH[i].w * c2_));     \
+    _Pragma("unroll") for (int i = 0; i < IT; ++i) OUT[i] = ln_dx4(GY[i], XH[i], c1_, c2_, R);            \
   }
 
 template <int IT>
@@ -310,7 +291,7 @@ k_ln_add_ln_bwd(const float* __restrict__ g_xout, const void* __restrict__ g_h, 
       if (j < C) {
         float4 a = *reinterpret_cast<const float4*>(xout + row * C + j), g = make_float4(0.f, 0.f, 0.f, 0.f);
         if (g_h) g = ln_ld4(g_h, gh_dt, row * C + j);
-        xh[i] = make_float4((a.x - st.z) * st.w, (a.y - st.z) * st.w, (a.z - st.z) * st.w, (a.w - st.z) * st.w);
+        xh[i] = ln_xhat4(a, st.z, st.w);
         const float4 gm1 = *reinterpret_cast<const float4*>(&gam[1][j]);
         gy[i] = make_float4(g.x * gm1.x, g.y * gm1.y, g.z * gm1.z, g.w * gm1.w);
         dg1[i].x += g.x * xh[i].x; dg1[i].y += g.y * xh[i].y; dg1[i].z += g.z * xh[i].z; dg1[i].w += g.w * xh[i].w;
@@ -335,7 +316,7 @@ k_ln_add_ln_bwd(const float* __restrict__ g_xout, const void* __restrict__ g_h, 
       xh[i] = make_float4(0.f, 0.f, 0.f, 0.f); gy[i] = xh[i];
       if (j < C) {
         float4 a = ln_ld4(t, t_dt, row * C + j);
-        xh[i] = make_float4((a.x - st.x) * st.y, (a.y - st.x) * st.y, (a.z - st.x) * st.y, (a.w - st.x) * st.y);
+        xh[i] = ln_xhat4(a, st.x, st.y);
         const float4 gm0 = *reinterpret_cast<const float4*>(&gam[0][j]);
         gy[i] = make_float4(gv[i].x * gm0.x, gv[i].y * gm0.y, gv[i].z * gm0.z, gv[i].w * gm0.w);
         dg0[i].x += gv[i].x * xh[i].x; dg0[i].y += gv[i].y * xh[i].y; dg0[i].z += gv[i].z * xh[i].z; dg0[i].w += gv[i].w * xh[i].w;
@@ -409,10 +390,6 @@ extern "C" int ss_ln_add_ln_bwd(const float* g_xout, const void* g_h, int g_h_dt
 // wave-per-row, lane-per-4-columns mapping as the LayerNorm backward: per-lane register partials
 // over a grid-stride row loop, LDS reduction across the block's waves, one partial row per block.
 // =====================================================================================
-__device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752f)); }
-__device__ __forceinline__ float dgelu_f(float z) {
-  return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * __expf(-0.5f * z * z);
-}
 
 template <int IT>
 __device__ __forceinline__ void col_partials_store(float4 (&a)[IT], float4 (&b)[IT], float* pa, float* pb, int C) {
@@ -745,17 +722,6 @@ extern "C" int ss_bn_bwd_finish(const float* part, int nblocks, int channels, in
 // HBM-bound: 16-byte lanes, eight (bf16) or four (fp32) elements per thread.  Why it is not an epilogue of the fc1 GEMM: DESIGN.md
 // section 4 ("Why the exact-erf GELU is not in a GEMM epilogue").
 // =====================================================================================
-__device__ __forceinline__ float dgelu_exact(float z) {
-  return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.3989422804014327f * expf(-0.5f * z * z);
-}
-__device__ __forceinline__ void bf8_unpack(const uint4& u, float (&v)[8]) {
-  v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u); v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-  v[4] = __uint_as_float(u.z << 16); v[5] = __uint_as_float(u.z & 0xffff0000u); v[6] = __uint_as_float(u.w << 16); v[7] = __uint_as_float(u.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 bf8_pack(const float (&v)[8]) {
-  uint4 o; o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]); o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
-  return o;
-}
 
 template <bool BWD>
 __global__ void __launch_bounds__(256)

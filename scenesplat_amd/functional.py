@@ -621,6 +621,13 @@ def register_transposed(weights):
             ent[1] = None                     # force the next refresh to write both copies
 
 
+def unregister_transposed(weights):
+    """Drop the (in, out) copies of these weights: their layers run the NN form of the dgrad GEMM again."""
+    for p in weights:
+        if p in _SHADOW_T:
+            del _SHADOW_T[p]
+
+
 def bf16_t_of(p):
     """The transposed bf16 copy of a registered Linear weight while its shadow is current, else None."""
     if not isinstance(p, torch.nn.Parameter):
@@ -1035,6 +1042,152 @@ def add_layer_norm(x, y, rowscale=None, gamma=None, beta=None, eps=1e-5, want_co
         ga, be = gamma, beta
         stage = _eff_stage(ga, be) if ga is not None else None
     return _AddLayerNorm.apply(x, y, rowscale, ga, be, eps, want_copy, h_dtype, stage)
+
+
+# ---- fused Block tail: proj + residual + LN2 + fc1 + GELU + fc2 + residual in one launch each way (csrc/block_tail.hip) ----------
+BLOCK_TAIL_CHANNELS = (32, 64, 128, 256)
+# Widest level that runs fused.  64: the HBM-bound levels (enc0, enc1), where the pair takes 0.24 / 0.51 of the chain's kernel time.  At
+# 128 the census gain is 0.05 ms per step and at 256 the pair only ties (a tile streams 1.2 MB of weights through one CU): the in-process
+# A/B cannot tell either from its spread (profiles/block_tail.md), so they stay on the seam path until that form is faster.
+BLOCK_TAIL_MAX_CHANNELS = int(os.environ.get("SS_BLOCK_TAIL_MAX_CHANNELS", "64"))
+BLOCK_TAIL_CALLS = 0          # fused forwards so far (tests read it to see which path a Block took)
+
+
+def block_tail_rows():
+    """Rows one workgroup of the fused pair owns (the kernels' row tile)."""
+    return int(nv.lib().ss_block_tail_rows())
+
+
+def block_tail_fwd_raw(feat, x, rs1, rs2, wp, bp, w1, b1, w2, b2, gamma, beta, eps, want_copy):
+    """ss_block_tail_fwd on raw operands (bf16 feat / weights, f32 x / affine, the three biases all f32 or all bf16) -> dict of
+    everything it writes."""
+    n, C = x.shape
+    H = 4 * C
+    rq = nv._req
+    rq(feat, torch.bfloat16, "feat", (n, C)); rq(x, torch.float32, "x")
+    rq(wp, torch.bfloat16, "wp", (C, C)); rq(w1, torch.bfloat16, "w1", (H, C)); rq(w2, torch.bfloat16, "w2", (C, H))
+    rq(bp, None, "bp", (C,)); rq(b1, bp.dtype, "b1", (H,)); rq(b2, bp.dtype, "b2", (C,))
+    rq(gamma, torch.float32, "gamma", (C,)); rq(beta, torch.float32, "beta", (C,))
+    for t, nm in ((rs1, "rs1"), (rs2, "rs2")):
+        if t is not None:
+            rq(t, torch.float32, nm, (n,))
+    dev = x.device
+    o = dict(x_mid=torch.empty((n, C), dtype=torch.float32, device=dev), mean=torch.empty(n, dtype=torch.float32, device=dev),
+             rstd=torch.empty(n, dtype=torch.float32, device=dev), h2=torch.empty((n, C), dtype=torch.bfloat16, device=dev),
+             u=torch.empty((n, H), dtype=torch.bfloat16, device=dev), a=torch.empty((n, H), dtype=torch.bfloat16, device=dev),
+             x_out=torch.empty((n, C), dtype=torch.float32, device=dev),
+             xcopy=torch.empty((n, C), dtype=torch.bfloat16, device=dev) if want_copy else None)
+    p = nv._p
+    nv.check(nv.lib().ss_block_tail_fwd(p(feat), p(x), p(rs1), p(rs2), p(wp), p(bp), p(w1), p(b1), p(w2), p(b2), nv.dtype_code(bp), p(gamma), p(beta),
+                                        float(eps), p(o["x_mid"]), p(o["mean"]), p(o["rstd"]), p(o["h2"]), p(o["u"]), p(o["a"]),
+                                        p(o["x_out"]), p(o["xcopy"]), n, C, nv._stream()), "ss_block_tail_fwd")
+    return o
+
+
+def block_tail_bwd_raw(g_xout, g_xcopy, x_mid, mean, rstd, u, rs1, rs2, gamma, wpt, w1t, w2t, nblocks=None):
+    """ss_block_tail_bwd -> (g_mid f32, dfeat, dy2, du, dy1 bf16, part (2, nb, C) f32 partial sums of dgamma / dbeta)."""
+    n, C = x_mid.shape
+    H = 4 * C
+    rq = nv._req
+    rq(g_xout, torch.float32, "g_xout", (n, C)); rq(x_mid, torch.float32, "x_mid"); rq(u, torch.bfloat16, "u", (n, H))
+    rq(mean, torch.float32, "mean", (n,)); rq(rstd, torch.float32, "rstd", (n,)); rq(gamma, torch.float32, "gamma", (C,))
+    rq(wpt, torch.bfloat16, "wp_t", (C, C)); rq(w1t, torch.bfloat16, "w1_t", (C, H)); rq(w2t, torch.bfloat16, "w2_t", (H, C))
+    if g_xcopy is not None:
+        rq(g_xcopy, torch.bfloat16, "g_xcopy", (n, C))
+    for t, nm in ((rs1, "rs1"), (rs2, "rs2")):
+        if t is not None:
+            rq(t, torch.float32, nm, (n,))
+    dev = x_mid.device
+    nb = int(nv.lib().ss_block_tail_bwd_blocks(n)) if nblocks is None else int(nblocks)    # (fewer: a workgroup walks several tiles)
+    g_mid = torch.empty((n, C), dtype=torch.float32, device=dev)
+    dfeat, dy2, dy1 = (torch.empty((n, C), dtype=torch.bfloat16, device=dev) for _ in range(3))
+    du = torch.empty((n, H), dtype=torch.bfloat16, device=dev)
+    part = torch.empty((2, nb, C), dtype=torch.float32, device=dev)
+    p = nv._p
+    nv.check(nv.lib().ss_block_tail_bwd(p(g_xout), p(g_xcopy), p(x_mid), p(mean), p(rstd), p(u), p(rs1), p(rs2), p(gamma), p(wpt),
+                                        p(w1t), p(w2t), p(g_mid), p(dfeat), p(dy2), p(du), p(dy1), p(part), n, C, nb, nv._stream()),
+             "ss_block_tail_bwd")
+    return g_mid, dfeat, dy2, du, dy1, part
+
+
+class _BlockTail(torch.autograd.Function):
+    """(feat, x) -> (x_out, bf16 copy | None).  wp .. beta are the parameters or their stage aliases (gradient routing only); ops =
+    the bf16 operands (wp16, w116, w216, wp16t, w116t, w216t, bp16, b116, b216: the shadows the six-launch chain's GEMMs read).  The backward kernel hands back the input gradients and the three
+    weight-gradient operands; the parameter side then runs as _linear_backward / _AddLayerNorm.backward do."""
+
+    @staticmethod
+    def forward(ctx, feat, x, rs1, rs2, wp, bp, w1, b1, w2, b2, gamma, beta, eps, want_copy, stage, ops):
+        global BLOCK_TAIL_CALLS
+        BLOCK_TAIL_CALLS += 1
+        feat, x = feat.contiguous(), x.contiguous()
+        g32 = gamma.detach().contiguous()
+        o = block_tail_fwd_raw(feat, x, rs1, rs2, ops[0], ops[6], ops[1], ops[7], ops[2], ops[8], g32, beta.detach().contiguous(), eps,
+                               want_copy)
+        ctx.save_for_backward(feat, o["x_mid"], o["mean"], o["rstd"], o["h2"], o["u"], o["a"], rs1, rs2, g32, ops[3], ops[4], ops[5])
+        ctx.stage = stage
+        ctx.set_materialize_grads(False)
+        return o["x_out"], o["xcopy"]
+
+    @staticmethod
+    def backward(ctx, g_xout, g_xcopy):
+        feat, x_mid, mean, rstd, h2, u, a, rs1, rs2, g32, wpt, w1t, w2t = ctx.saved_tensors
+        if g_xout is None and g_xcopy is None:
+            return (None,) * 16
+        g_xout = g_xout.float().contiguous() if g_xout is not None else torch.zeros_like(x_mid)
+        g_xcopy = g_xcopy.contiguous().to(torch.bfloat16) if g_xcopy is not None else None
+        g_mid, dfeat, dy2, du, dy1, part = block_tail_bwd_raw(g_xout, g_xcopy, x_mid, mean, rstd, u, rs1, rs2, g32, wpt, w1t, w2t)
+        need = ctx.needs_input_grad
+        stage = ctx.stage
+        # weight / bias gradients: queued on the stage (one grouped launch when the backward leaves it), else today's fallbacks
+        _, dwp, dbp = _linear_backward(feat, None, False, torch.float32, True, stage, dy1, False, need[4], need[5])
+        _, dw1, db1 = _linear_backward(h2, None, False, torch.float32, True, stage, du, False, need[6], need[7])
+        _, dw2, db2 = _linear_backward(a, None, False, torch.float32, True, stage, dy2, False, need[8], need[9])
+        dg = db = None
+        if need[10] or need[11]:
+            if stage is not None:
+                dst = torch.empty((2, part.shape[2]), dtype=torch.float32, device=part.device)
+                stage.redq.append((part, dst))
+                _UNFLUSHED.add(stage)
+                dg, db = dst[0], dst[1]
+            else:
+                red = part.sum(1)
+                dg, db = red[0], red[1]
+        return (dfeat if need[0] else None, g_mid if need[1] else None, None, None, dwp, dbp, dw1, db1, dw2, db2, dg, db,
+                None, None, None, None)
+
+
+def block_tail_eligible(x, proj, ln2, fc1, fc2):
+    """Can the tail of a Block with these modules run on the fused pair: width in the instantiated set (and at most
+    BLOCK_TAIL_MAX_CHANNELS), hidden = 4C, plain fp32 affine nn.LayerNorm / biased nn.Linear parameters on the GPU, and the bf16
+    shadows with their (in, out) copies registered and current (the dgrad products read the transposed copies)."""
+    C = x.shape[1]
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and C in BLOCK_TAIL_CHANNELS and C <= BLOCK_TAIL_MAX_CHANNELS):
+        return False
+    if type(ln2) is not torch.nn.LayerNorm or ln2.weight is None or ln2.bias is None or tuple(ln2.normalized_shape) != (C,):
+        return False
+    if tuple(proj.weight.shape) != (C, C) or tuple(fc1.weight.shape) != (4 * C, C) or tuple(fc2.weight.shape) != (C, 4 * C):
+        return False
+    for p in (proj.weight, proj.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, ln2.weight, ln2.bias):
+        if not isinstance(p, torch.nn.Parameter) or p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
+            return False
+    for w in (proj.weight, fc1.weight, fc2.weight):
+        ent = _SHADOW.get(w)
+        if ent is None or not _shadow_current(ent, w) or bf16_t_of(w) is None:
+            return False
+    return True
+
+
+def block_tail(feat, x, rs1, rs2, proj, ln2, fc1, fc2, want_copy=False):
+    """The tail of a pre-norm Block from the attention output `feat` (n, C) on: x + rs1 proj(feat) -> LN2 -> fc1 -> GELU -> fc2 ->
+    second residual, fused (callers check block_tail_eligible first).  -> (x_out fp32, bf16 copy of x_out | None)."""
+    params = (proj.weight, proj.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, ln2.weight, ln2.bias)
+    routed = [_routed(p) for p in params] if torch.is_grad_enabled() else [(p, None) for p in params]
+    stage = routed[0][1]
+    if stage is None or any(s is not stage for _, s in routed):
+        stage, routed = None, [(p, None) for p in params]
+    ops = tuple(bf16_of(w) for w in (proj.weight, fc1.weight, fc2.weight)) + tuple(bf16_t_of(w) for w in (proj.weight, fc1.weight, fc2.weight)) \
+        + tuple(bf16_of(b) for b in (proj.bias, fc1.bias, fc2.bias))
+    return _BlockTail.apply(feat.to(torch.bfloat16), x, rs1, rs2, *[a for a, _ in routed], ln2.eps, want_copy, stage, ops)
 
 
 class _BatchNormAct(torch.autograd.Function):

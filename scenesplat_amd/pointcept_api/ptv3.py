@@ -33,7 +33,8 @@ from .structure import Point
 # knobs of the execution (not of the model): attention kernel family and conv compute dtype
 RUNTIME = dict(attn_impl=nv.ATTN_SIMT, conv_dtype=None,  # conv_dtype: None = fp32 per-tap path (reference), torch.bfloat16, or "bf16x3"
                attn_headmajor=os.environ.get("SS_ATTN_HM", "1") != "0",   # MFMA attention on the head-major layout (round 3)
-               param_shadows=os.environ.get("SS_PARAM_SHADOWS", "1") != "0")   # bf16 weight shadows under autocast
+               param_shadows=os.environ.get("SS_PARAM_SHADOWS", "1") != "0",   # bf16 weight shadows under autocast
+               fuse_block_tail=os.environ.get("SS_BLOCK_TAIL", "1") != "0")    # proj .. second residual of a Block in one launch each way (C <= SF.BLOCK_TAIL_MAX_CHANNELS)
 
 
 def bench_runtime():
@@ -149,7 +150,7 @@ class SerializedAttention(PointModule):
             raise ValueError("enable_rpe: every batch element needs at least one point")
         return k
 
-    def _forward_rpe(self, x, level):
+    def _forward_rpe(self, x, level, pre_proj=False):
         win = level.window(self.order_index, self.rpe_window_size(level))
         qkv = _lin(self.qkv, x)
         bf16 = (x.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16) \
@@ -161,11 +162,12 @@ class SerializedAttention(PointModule):
         a = qkv.to(torch.bfloat16) if bf16 else qkv
         feat = SF.window_attention_rpe(a, win, level.grid_coord, self.rpe.rpe_table, self.rpe.pos_bnd, self.num_heads,
                                        self.scale, impl).to(qkv.dtype)
-        return _lin(self.proj, feat)
+        return feat if pre_proj else _lin(self.proj, feat)
 
-    def forward(self, x, level):
+    def forward(self, x, level, pre_proj=False):
+        """pre_proj: return the attention output BEFORE self.proj (the fused Block tail applies the projection itself)."""
         if self.enable_rpe:
-            return self._forward_rpe(x, level)
+            return self._forward_rpe(x, level, pre_proj)
         win = level.window(self.order_index, self.patch_size)
         impl = RUNTIME["attn_impl"]
         if (impl == nv.ATTN_MFMA and RUNTIME.get("attn_headmajor", True) and x.is_cuda and torch.is_autocast_enabled()
@@ -173,13 +175,13 @@ class SerializedAttention(PointModule):
                 and (self.channels // self.num_heads) in (16, 32, 48, 64)):
             # round 3: projection -> head-major, window-ordered q / k / v -> LDS-DMA attention kernels (csrc/attention_hm.hip)
             feat = SF.qkv_window_attention(x, self.qkv.weight, self.qkv.bias, win, self.num_heads, self.scale)
-            return _lin(self.proj, feat)
+            return feat if pre_proj else _lin(self.proj, feat)
         qkv = _lin(self.qkv, x)
         if impl == nv.ATTN_MFMA and qkv.dtype != torch.bfloat16:
             feat = SF.window_attention(qkv.to(torch.bfloat16), win, self.num_heads, self.scale, impl).to(qkv.dtype)
         else:
             feat = SF.window_attention(qkv, win, self.num_heads, self.scale, impl)
-        return _lin(self.proj, feat)
+        return feat if pre_proj else _lin(self.proj, feat)
 
 
 class MLP(nn.Module):
@@ -231,9 +233,30 @@ class Block(PointModule):
         else:
             t = SF.layer_norm(t, ln0.weight, ln0.bias, ln0.eps)
             x, h, _ = SF.add_layer_norm(x, t, None, ln1.weight, ln1.bias, ln1.eps, False, hdt)
+        if self._tail_fusable(x, ln2):
+            # proj + residual + LN2 + fc1 + GELU + fc2 + residual: one launch each way (csrc/block_tail.hip); the two DropPath
+            # scales are drawn / popped in the order of the two seams below
+            feat = self.attn(h, level, pre_proj=True)
+            rs1, rs2 = self._row_scale(x), self._row_scale(x)
+            mlp = self.mlp[0]
+            return SF.block_tail(feat, x, rs1, rs2, self.attn.proj, ln2, mlp.fc1, mlp.fc2, want_copy)
         x, h, _ = SF.add_layer_norm(x, self.attn(h, level), self._row_scale(x), ln2.weight, ln2.bias, ln2.eps, False, hdt)
         x, _, xb = SF.add_layer_norm(x, self.mlp(h), self._row_scale(x), None, None, 0.0, want_copy, hdt)
         return x, xb
+
+    def _tail_fusable(self, x, ln2):
+        """The fused Block tail (SF.block_tail) covers: bf16 autocast with the fused seams on, C in {32, 64, 128, 256} up to
+        SF.BLOCK_TAIL_MAX_CHANNELS, hidden = 4C, exact-erf nn.GELU, plain fp32 nn.LayerNorm / nn.Linear parameters (a PDNorm-resolved
+        LN2 takes the seam path) whose bf16 shadows and (in, out) copies are registered and current."""
+        if not (RUNTIME.get("fuse_block_tail", True) and RUNTIME.get("fuse_ln_seam", True) and x.is_cuda
+                and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+            return False
+        mlp = self.mlp[0]
+        if isinstance(self.norm2[0], PDNorm):
+            return False
+        if not (isinstance(mlp, MLP) and type(mlp.act) is nn.GELU and getattr(mlp.act, "approximate", "none") == "none"):
+            return False
+        return SF.block_tail_eligible(x, self.attn.proj, ln2, mlp.fc1, mlp.fc2)
 
     def _row_scale(self, x):
         dp = self.drop_path[0]
@@ -496,7 +519,10 @@ class PointTransformerV3(PointModule):
     def _refresh_shadows(self):
         """bf16 copies of every Linear / SubMConv3d weight and Linear bias, refreshed with multi-tensor copies."""
         ps = self.__dict__.get("_shadow_lists")
-        if ps is None or ps[2] != next(self.parameters()).device:
+        # the fused Block tail's (in, out) copies are registered with the shadows, for exactly the Blocks that can take it: redone
+        # when the switch or the channel bound changes, so that every other Block keeps today's dgrad form
+        tail = SF.BLOCK_TAIL_MAX_CHANNELS if RUNTIME.get("fuse_block_tail", True) else 0
+        if ps is None or ps[2] != next(self.parameters()).device or ps[4] != tail:
             params, skip = [], self._modulation_linears()
             for m in self.modules():
                 if isinstance(m, nn.Linear) and id(m) not in skip:
@@ -511,12 +537,21 @@ class PointTransformerV3(PointModule):
                     wide += [m.weight for m in st.modules() if isinstance(m, nn.Linear) and m.weight.numel() >= 65536]
             if RUNTIME.get("dgrad_nt", True):
                 SF.register_transposed(wide)
+            # the fused Block tail reads the (in, out) copies of proj / fc1 / fc2 in its three dgrad products
+            keep = {id(w) for w in wide} if RUNTIME.get("dgrad_nt", True) else set()
+            mine = [w for m in self.modules() if isinstance(m, Block) and m.channels in SF.BLOCK_TAIL_CHANNELS and m.channels <= tail
+                    and m.pre_norm and not isinstance(m.norm2[0], PDNorm)
+                    and tuple(m.mlp[0].fc1.weight.shape) == (4 * m.channels, m.channels)
+                    for w in (m.attn.proj.weight, m.mlp[0].fc1.weight, m.mlp[0].fc2.weight) if id(w) not in keep]
+            SF.unregister_transposed([w for w in self.__dict__.get("_tail_transposed", []) if id(w) not in {id(v) for v in mine}])
+            SF.register_transposed(mine)
+            self.__dict__["_tail_transposed"] = mine
             # dgrad weights of the convs that run on plain bf16 operands: mirrored once per refresh instead of once per backward call
             SF.register_mirrored([m.weight for m in self.modules() if isinstance(m, SubMConv3d)
                                   and conv_dtype_for(m.weight.shape[0]) == torch.bfloat16])
             # fp32 accumulators of the weight / bias gradients: one zero-filled arena per step
             total = sum(((p.numel() + 3) & ~3) for p in params if p is not None) + 4 * len(params)
-            ps = (src, dst, next(self.parameters()).device, total)
+            ps = (src, dst, next(self.parameters()).device, total, tail)
             self.__dict__["_shadow_lists"] = ps
         SF.refresh_shadows(ps[0], ps[1])
         if torch.is_grad_enabled():

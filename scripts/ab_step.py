@@ -62,6 +62,13 @@ def setter(on):
         SF.HM_FUSED_MIN_ROWS = 1024 if on else 4096
     elif which == "hm_ch":            # ... and from 64 channels on (enc1: 25,600 x 64)
         SF.HM_FUSED_MIN_CHANNELS = 64 if on else 128
+    elif which == "block_tail":       # proj .. second residual of the Blocks up to SF.BLOCK_TAIL_MAX_CHANNELS (64): one launch each way;
+        # off = the seam path with the NN dgrad form (the model drops the tail's transposed copies on the next forward)
+        RUNTIME["fuse_block_tail"] = on
+    elif which == "block_tail_256":   # ... also at 256 channels (enc3, dec2) against only up to 128
+        SF.BLOCK_TAIL_MAX_CHANNELS = 256 if on else 128
+    elif which == "block_tail_128":   # ... also at 128 and 256 channels (enc2, enc3, dec2) against the default bound of 64
+        SF.BLOCK_TAIL_MAX_CHANNELS = 256 if on else 64
     elif which == "mask_small":
         import scenesplat_amd.plan as P
         P.CONV_MASK_MIN_SITES = 4096 if on else 16384
@@ -100,5 +107,6 @@ for b in range(blocks):
         step()
     torch.cuda.synchronize()
     res[on].append((time.perf_counter() - t0) / steps * 1e3)
-print(which, "ON ", " ".join(f"{v:.1f}" for v in res[True]), " mean %.2f" % (sum(res[True]) / len(res[True])))
-print(which, "OFF", " ".join(f"{v:.1f}" for v in res[False]), " mean %.2f" % (sum(res[False]) / len(res[False])))
+print(which, "ON ", " ".join(f"{v:.2f}" for v in res[True]), " mean %.2f" % (sum(res[True]) / len(res[True])))
+print(which, "OFF", " ".join(f"{v:.2f}" for v in res[False]), " mean %.2f" % (sum(res[False]) / len(res[False])))
+print(which, "spread between repeated blocks: ON %.2f  OFF %.2f ms" % (max(res[True]) - min(res[True]), max(res[False]) - min(res[False])))
