@@ -88,6 +88,8 @@ extern "C" int ss_stream_create_cu_mask(int nwords, const uint32_t* mask, void**
   return SS_OK;
 }
 
+// Lane width of gather / scatter: the widest of 16 / 4 / 2 bytes that divides the row AND that both base pointers are aligned
+// to (a contiguous bf16 view with an odd storage offset has an even row width on a 2-byte-aligned address).
 extern "C" int ss_gather_rows(const void* src, const int32_t* idx, void* dst, int64_t n_dst, int64_t row_bytes,
                               hipStream_t stream) {
   if (n_dst < 0 || row_bytes <= 0 || (row_bytes & 1)) return SS_ERR_ARG;
@@ -96,7 +98,7 @@ extern "C" int ss_gather_rows(const void* src, const int32_t* idx, void* dst, in
     int chunks = (int)(row_bytes >> 4);
     SS_LAUNCH(k_gather_rows<uint4>, dim3(ss_div_up(n_dst * chunks, 256)), dim3(256), 0, stream,
                        (const uint4*)src, idx, (uint4*)dst, n_dst, chunks);
-  } else if ((row_bytes & 3) == 0) {
+  } else if ((row_bytes & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 3) == 0) {
     int chunks = (int)(row_bytes >> 2);
     SS_LAUNCH(k_gather_rows<uint32_t>, dim3(ss_div_up(n_dst * chunks, 256)), dim3(256), 0, stream,
                        (const uint32_t*)src, idx, (uint32_t*)dst, n_dst, chunks);
@@ -116,7 +118,7 @@ extern "C" int ss_scatter_rows(const void* src, const int32_t* idx, void* dst, i
     int chunks = (int)(row_bytes >> 4);
     SS_LAUNCH(k_scatter_rows<uint4>, dim3(ss_div_up(n_src * chunks, 256)), dim3(256), 0, stream,
                        (const uint4*)src, idx, (uint4*)dst, n_src, chunks);
-  } else if ((row_bytes & 3) == 0) {
+  } else if ((row_bytes & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 3) == 0) {
     int chunks = (int)(row_bytes >> 2);
     SS_LAUNCH(k_scatter_rows<uint32_t>, dim3(ss_div_up(n_src * chunks, 256)), dim3(256), 0, stream,
                        (const uint32_t*)src, idx, (uint32_t*)dst, n_src, chunks);
