@@ -19,17 +19,11 @@
 //
 // Forward math: attention_mfma32.hip's (S^T = K Q^T on v_mfma_f32_32x32x16_bf16 with the query on the lane, lane-local online
 // softmax with a lazily moved maximum, P^T handed to O^T += V^T P^T from the accumulators, row sums through a ones column).
-#include "attention_internal.h"
+// Operand types, MFMA32, as_bf8 / cat_tr, max3 / swap32 and xcd_remap: attention_frag.h; the LDS-DMA wrappers and the plane
+// geometry (HMC / HMPlan) are this file's own.
+#include "attention_frag.h"
 #include "../../include/scenesplat_hip.h"
 #include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 hbf8_t;
-typedef __attribute__((ext_vector_type(4))) short hs4_t;
-typedef __attribute__((ext_vector_type(8))) short hs8_t;
-typedef __attribute__((address_space(3))) hs4_t hlds_s4_t;
-
-#define HM_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-#define HM_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
 #ifndef HM_THR
 #define HM_THR 6.0f            // lazy-rescale threshold in exp2 units (P <= 64)
@@ -64,22 +58,6 @@ template <int D, int NW = HM_WAVES> struct HMC {
   static constexpr int NKP = CH * (HM_BK / 64);            // K pieces of a tile
 };
 
-__device__ __forceinline__ hbf8_t hm_bf8(uint4 v) { return __builtin_bit_cast(hbf8_t, v); }
-__device__ __forceinline__ hs4_t hm_tr(const char* addr) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(addr)); }
-__device__ __forceinline__ hbf8_t hm_cat(hs4_t lo, hs4_t hi) {
-  hs8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(hbf8_t, v);
-}
-__device__ __forceinline__ float hm_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float hm_swap32(float v) {     // value of lane ^ 32
-  unsigned int u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
-}
-__device__ __forceinline__ int hm_xcd(int bid, int nb) {
-  int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, slot = bid >> 3;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-}
 // LDS-DMA as inline asm (wgrad8.hip: with the builtin hipcc drains vmcnt in front of every transposed read)
 __device__ __forceinline__ void hm_glds16(const void* gsrc, unsigned lds_wave_base) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_wave_base) : "memory");
@@ -92,11 +70,6 @@ __device__ __forceinline__ const char* hm_uniform_ptr(const void* p) {
   uint64_t u = (uint64_t)(uintptr_t)p;
   uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
   return reinterpret_cast<const char*>((uintptr_t)(((uint64_t)hi << 32) | lo));
-}
-__device__ __forceinline__ float hm_bf16_round(float x) { return __uint_as_float(pack_bf16x2(x, 0.f) << 16); }
-__device__ __forceinline__ unsigned int hm_hi_lo(float x) {     // x ~= hi + lo, both bf16: packed {hi, lo}
-  float hi = hm_bf16_round(x);
-  return pack_bf16x2(hi, x - hi);
 }
 
 // ---- DMA plan of one wave: NPW pieces per (row operand with CH chunk planes | tr operand with NCB column-block planes) tile ----
@@ -133,7 +106,7 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
   constexpr int THREADS = 64 * NW, BQ = 32 * NW * NQ;
   __shared__ __attribute__((aligned(256))) char smem[A::LDS];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, hh = lane >> 5;
-  const int lid = hm_xcd(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int qc = lid % qchunks; const int t_ = lid / qchunks; const int h = t_ % H; const int w = t_ / H;
   const int p0 = win_start[w], L = win_start[w + 1] - p0;
   const int q0 = qc * BQ;
@@ -172,13 +145,13 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
   // ---- Q fragments (B operand of S^T = K Q^T): lane (query lr, half hh) of sub-tile u holds Q[q][16 ks + 8 hh .. +7] ----
   int qslot[NQ];
   int32_t srow[NQ];
-  hbf8_t qf[NQ][A::NKS];
+  bf8_t qf[NQ][A::NKS];
 #pragma unroll
   for (int u = 0; u < NQ; ++u) {
     qslot[u] = q0 + (wave * NQ + u) * 32 + lr;
     const unsigned short* qp = qbase + (int64_t)min(qslot[u], L - 1) * D + 8 * hh;
 #pragma unroll
-    for (int ks = 0; ks < A::NKS; ++ks) qf[u][ks] = hm_bf8(*reinterpret_cast<const uint4*>(qp + 16 * ks));
+    for (int ks = 0; ks < A::NKS; ++ks) qf[u][ks] = as_bf8(*reinterpret_cast<const uint4*>(qp + 16 * ks));
     srow[u] = qslot[u] < L ? sidx[p0 + qslot[u]] : -1;
   }
 
@@ -222,10 +195,10 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
   auto qk_block = [&](f32x16_t (&s)[NQ], const unsigned kb, const int IMM) {
 #pragma unroll
     for (int ks = 0; ks < A::NKS; ++ks) {
-      hbf8_t a = __builtin_bit_cast(hbf8_t, *(lds_u4_t*)(kb + ks * 2 * A::KPL + IMM * 16));
+      bf8_t a = __builtin_bit_cast(bf8_t, *(lds_u4_t*)(kb + ks * 2 * A::KPL + IMM * 16));
 #pragma unroll
       for (int u = 0; u < NQ; ++u) {
-        if (!(HM_ABL & 32)) s[u] = (ks == 0) ? HM_MFMA32(a, qf[u][ks], mneg[u]) : HM_MFMA32(a, qf[u][ks], s[u]);
+        if (!(HM_ABL & 32)) s[u] = (ks == 0) ? MFMA32(a, qf[u][ks], mneg[u]) : MFMA32(a, qf[u][ks], s[u]);
         else if (ks == 0) s[u] = mneg[u];
       }
     }
@@ -242,14 +215,14 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
           if (kv0 + (r & 3) + 8 * (r >> 2) + 4 * hh >= L) s[r] = -INFINITY;
       }
       if (HM_ABL & 8) continue;
-      float mx = hm_max3(s[0], s[1], s[2]);
+      float mx = max3(s[0], s[1], s[2]);
 #pragma unroll
-      for (int r = 3; r < 15; r += 2) mx = hm_max3(mx, s[r], s[r + 1]);
+      for (int r = 3; r < 15; r += 2) mx = max3(mx, s[r], s[r + 1]);
       mx = fmaxf(mx, s[15]);
       {   // maximum over the two half-waves: after the swap one of (a, b) is this lane's value, the other its partner's
         unsigned int uu = __float_as_uint(mx);
         auto r = __builtin_amdgcn_permlane32_swap(uu, uu, false, false);
-        mx = hm_max3(mx, __uint_as_float(r[0]), __uint_as_float(r[1]));
+        mx = max3(mx, __uint_as_float(r[0]), __uint_as_float(r[1]));
       }
       const float thr = first ? -INFINITY : HM_THR;
       if (__any(mx > thr)) {        // the shift moves only past the threshold; everything so far is rescaled exactly once
@@ -268,7 +241,7 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
     }
   };
   auto pv_block = [&](f32x16_t (&sv)[NQ], const unsigned (&vb)[A::NMT], const int IMM) {
-    hbf8_t pf[NQ][2];
+    bf8_t pf[NQ][2];
 #pragma unroll
     for (int u = 0; u < NQ; ++u) {
       f32x16_t& s = sv[u];
@@ -286,7 +259,7 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
         uint4 pk;
         pk.x = pack_bf16x2(s[8 * ss + 0], s[8 * ss + 1]); pk.y = pack_bf16x2(s[8 * ss + 2], s[8 * ss + 3]);
         pk.z = pack_bf16x2(s[8 * ss + 4], s[8 * ss + 5]); pk.w = pack_bf16x2(s[8 * ss + 6], s[8 * ss + 7]);
-        pf[u][ss] = hm_bf8(pk);
+        pf[u][ss] = as_bf8(pk);
       }
     }
     // O^T += V^T P^T; element j of lane half hh in step ss <-> key 16 ss + 8 (j>>2) + 4 hh + (j&3) of the block
@@ -300,10 +273,10 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
 #pragma unroll
       for (int mt = 0; mt < A::NMT; ++mt) {
         const unsigned va = vb[mt] + (IMM + 16 * ss) * 32;
-        hbf8_t vf = hm_cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(va)),
-                           __builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(va + 8 * 32)));
+        bf8_t vf = cat_tr(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(va)),
+                          __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(va + 8 * 32)));
 #pragma unroll
-        for (int u = 0; u < NQ; ++u) o[u][mt] = HM_MFMA32(vf, pf[u][ss], o[u][mt]);
+        for (int u = 0; u < NQ; ++u) o[u][mt] = MFMA32(vf, pf[u][ss], o[u][mt]);
       }
     }
   };
@@ -361,10 +334,10 @@ k_attn_hm_fwd(const unsigned short* __restrict__ hm, int64_t NP, const int32_t* 
     float lt;
     if (A::PADCOL) {
       constexpr int LR = D % 32, REG = (LR >> 3) * 4 + (LR & 3), HF = (LR >> 2) & 1;
-      float mine = o[u][D / 32][REG], other = hm_swap32(mine);
+      float mine = o[u][D / 32][REG], other = swap32(mine);
       lt = (hh == HF) ? mine : other;
     } else {
-      lt = lsum[u] + hm_swap32(lsum[u]);
+      lt = lsum[u] + swap32(lsum[u]);
     }
     if (qslot[u] < L) {
       // -lse in exp2 units: the backward kernels start their score accumulators from it (C operand of the first MFMA).  A BORROWED
@@ -470,7 +443,7 @@ k_attn_hm_dq(const unsigned short* __restrict__ hm, int64_t NP, const unsigned s
   typedef __attribute__((ext_vector_type(4))) unsigned int hu32x4_t;
   typedef const __attribute__((address_space(3))) hu32x4_t lds_u4_t;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, hh = lane >> 5;
-  const int lid = hm_xcd(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int qc = lid % qchunks; const int t_ = lid / qchunks; const int h = t_ % H; const int w = t_ / H;
   const int p0 = win_start[w], L = win_start[w + 1] - p0;
   const int q0 = qc * HMQ_BQ;
@@ -502,19 +475,19 @@ k_attn_hm_dq(const unsigned short* __restrict__ hm, int64_t NP, const unsigned s
   const bool qok = qslot < L;
   int32_t srow = qok ? sidx[p0 + qslot] : -1;
   float nl = qok ? nlse2[hrow + qslot] : 0.f;
-  hbf8_t qf[A::NKS], gf[A::NKS];
+  bf8_t qf[A::NKS], gf[A::NKS];
   float dsum = 0.f;
   {
     const unsigned short* qp = qbase + (int64_t)min(qslot, L - 1) * D + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < A::NKS; ++ks) {
-      qf[ks] = hm_bf8(*reinterpret_cast<const uint4*>(qp + 16 * ks));
+      qf[ks] = as_bf8(*reinterpret_cast<const uint4*>(qp + 16 * ks));
       uint4 g = make_uint4(0, 0, 0, 0), o = make_uint4(0, 0, 0, 0);
       if (srow >= 0) {
         g = *reinterpret_cast<const uint4*>(dout + (int64_t)srow * C + h * D + 16 * ks + 8 * hh);
         o = *reinterpret_cast<const uint4*>(outp + (int64_t)srow * C + h * D + 16 * ks + 8 * hh);
       }
-      gf[ks] = hm_bf8(g);
+      gf[ks] = as_bf8(g);
       const unsigned int* ug = reinterpret_cast<const unsigned int*>(&g);
       const unsigned int* uo = reinterpret_cast<const unsigned int*>(&o);
 #pragma unroll
@@ -525,7 +498,7 @@ k_attn_hm_dq(const unsigned short* __restrict__ hm, int64_t NP, const unsigned s
       if (qok && doh) *reinterpret_cast<uint4*>(doh + (hrow + qslot) * D + 16 * ks + 8 * hh) = g;    // head-major copy for dK/dV (round-3 path)
     }
   }
-  float ndl = -(dsum + hm_swap32(dsum));
+  float ndl = -(dsum + swap32(dsum));
   if (qok && hh == 0) ndelta[hrow + qslot] = ndl;
   f32x16_t cl, cd;                       // C operands: sixteen registers of -lse2 / -delta of this lane's query
 #pragma unroll
@@ -560,10 +533,10 @@ k_attn_hm_dq(const unsigned short* __restrict__ hm, int64_t NP, const unsigned s
 #pragma unroll
     for (int ks = 0; ks < A::NKS; ++ks) {
       const int po = 2 * ks * A::PL + IMM * 16;
-      hbf8_t ka = __builtin_bit_cast(hbf8_t, *(lds_u4_t*)(rb + po));
-      hbf8_t va = __builtin_bit_cast(hbf8_t, *(lds_u4_t*)(rb + A::IMG + po));
-      s = (ks == 0) ? HM_MFMA32(ka, qf[ks], cl) : HM_MFMA32(ka, qf[ks], s);
-      dp = (ks == 0) ? HM_MFMA32(va, gf[ks], cd) : HM_MFMA32(va, gf[ks], dp);
+      bf8_t ka = __builtin_bit_cast(bf8_t, *(lds_u4_t*)(rb + po));
+      bf8_t va = __builtin_bit_cast(bf8_t, *(lds_u4_t*)(rb + A::IMG + po));
+      s = (ks == 0) ? MFMA32(ka, qf[ks], cl) : MFMA32(ka, qf[ks], s);
+      dp = (ks == 0) ? MFMA32(va, gf[ks], cd) : MFMA32(va, gf[ks], dp);
     }
     if (kv0 + 32 > L) {               // keys past the window end: P = 0 (last tile only; wave-uniform branch)
       asm volatile("; tail: mask keys past the window end" ::: "memory");
@@ -573,13 +546,13 @@ k_attn_hm_dq(const unsigned short* __restrict__ hm, int64_t NP, const unsigned s
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]) * dp[r];
-    hbf8_t df[2];
+    bf8_t df[2];
 #pragma unroll
     for (int ss = 0; ss < 2; ++ss) {
       uint4 pk;
       pk.x = pack_bf16x2(s[8 * ss + 0], s[8 * ss + 1]); pk.y = pack_bf16x2(s[8 * ss + 2], s[8 * ss + 3]);
       pk.z = pack_bf16x2(s[8 * ss + 4], s[8 * ss + 5]); pk.w = pack_bf16x2(s[8 * ss + 6], s[8 * ss + 7]);
-      df[ss] = hm_bf8(pk);
+      df[ss] = as_bf8(pk);
     }
     // dQ^T += K^T dS^T; element j of lane half hh in step ss <-> key 16 ss + 8 (j>>2) + 4 hh + (j&3) of the block
 #pragma unroll
@@ -587,9 +560,9 @@ k_attn_hm_dq(const unsigned short* __restrict__ hm, int64_t NP, const unsigned s
 #pragma unroll
       for (int mt = 0; mt < A::NMT; ++mt) {
         const unsigned ta = tb[mt] + (IMM + 16 * ss) * 16;
-        hbf8_t kt = hm_cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(ta)),
-                           __builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(ta + 8 * 16)));
-        dq[mt] = HM_MFMA32(kt, df[ss], dq[mt]);
+        bf8_t kt = cat_tr(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ta)),
+                          __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ta + 8 * 16)));
+        dq[mt] = MFMA32(kt, df[ss], dq[mt]);
       }
   };
 
@@ -691,7 +664,7 @@ k_attn_hm_dkv(const unsigned short* __restrict__ hm, int64_t NP, const unsigned 
   typedef __attribute__((ext_vector_type(4))) float hf32x4_t;
   typedef const __attribute__((address_space(3))) hf32x4_t lds_f4_t;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, hh = lane >> 5;
-  const int lid = hm_xcd(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int kc = lid % kchunks; const int t_ = lid / kchunks; const int h = t_ % H; const int w = t_ / H;
   const int p0 = win_start[w], L = win_start[w + 1] - p0;
   const int k0 = kc * HMK_BKEYS;
@@ -744,13 +717,13 @@ k_attn_hm_dkv(const unsigned short* __restrict__ hm, int64_t NP, const unsigned 
   // ---- this lane's key: K and V fragments (B operands): lane (key lr, half hh) holds K[key][16 ks + 8 hh .. +7] ----
   const int kslot = k0 + wave * 32 + lr;
   int32_t ksr = kslot < L ? sidx[p0 + kslot] : 0;
-  hbf8_t kf[A::NKS], vf[A::NKS];
+  bf8_t kf[A::NKS], vf[A::NKS];
   {
     const unsigned short* kp = hm + sec + (hrow + min(kslot, L - 1)) * D + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < A::NKS; ++ks) {
-      kf[ks] = hm_bf8(*reinterpret_cast<const uint4*>(kp + 16 * ks));
-      vf[ks] = hm_bf8(*reinterpret_cast<const uint4*>(kp + sec + 16 * ks));
+      kf[ks] = as_bf8(*reinterpret_cast<const uint4*>(kp + 16 * ks));
+      vf[ks] = as_bf8(*reinterpret_cast<const uint4*>(kp + sec + 16 * ks));
     }
   }
   asm volatile("" : "+v"(ksr));
@@ -791,14 +764,14 @@ k_attn_hm_dkv(const unsigned short* __restrict__ hm, int64_t NP, const unsigned 
 #pragma unroll
     for (int ks = 0; ks < A::NKS; ++ks) {
       const int po = 2 * ks * A::PL + IMM * 16;
-      hbf8_t qa = __builtin_bit_cast(hbf8_t, *(lds_u4_t*)(rb + po));
-      hbf8_t ga = __builtin_bit_cast(hbf8_t, *(lds_u4_t*)(rb + A::IMG + po));
-      s = HM_MFMA32(qa, kf[ks], s);
-      dp = HM_MFMA32(ga, vf[ks], dp);
+      bf8_t qa = __builtin_bit_cast(bf8_t, *(lds_u4_t*)(rb + po));
+      bf8_t ga = __builtin_bit_cast(bf8_t, *(lds_u4_t*)(rb + A::IMG + po));
+      s = MFMA32(qa, kf[ks], s);
+      dp = MFMA32(ga, vf[ks], dp);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) { s[r] = __builtin_amdgcn_exp2f(s[r]); dp[r] = s[r] * dp[r]; }
-    hbf8_t pf[2], df[2];
+    bf8_t pf[2], df[2];
 #pragma unroll
     for (int ss = 0; ss < 2; ++ss) {
       uint4 pk, dk_;
@@ -806,19 +779,19 @@ k_attn_hm_dkv(const unsigned short* __restrict__ hm, int64_t NP, const unsigned 
       pk.z = pack_bf16x2(s[8 * ss + 4], s[8 * ss + 5]); pk.w = pack_bf16x2(s[8 * ss + 6], s[8 * ss + 7]);
       dk_.x = pack_bf16x2(dp[8 * ss + 0], dp[8 * ss + 1]); dk_.y = pack_bf16x2(dp[8 * ss + 2], dp[8 * ss + 3]);
       dk_.z = pack_bf16x2(dp[8 * ss + 4], dp[8 * ss + 5]); dk_.w = pack_bf16x2(dp[8 * ss + 6], dp[8 * ss + 7]);
-      pf[ss] = hm_bf8(pk); df[ss] = hm_bf8(dk_);
+      pf[ss] = as_bf8(pk); df[ss] = as_bf8(dk_);
     }
 #pragma unroll
     for (int ss = 0; ss < 2; ++ss)
 #pragma unroll
       for (int mt = 0; mt < A::NMT; ++mt) {
         const unsigned ta = tb[mt] + (IMM + 16 * ss) * 16;
-        hbf8_t qt = hm_cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(ta)),
-                           __builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(ta + 8 * 16)));
-        hbf8_t gt = hm_cat(__builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(ta + A::IMG)),
-                           __builtin_amdgcn_ds_read_tr16_b64_v4i16((hlds_s4_t*)(ta + A::IMG + 8 * 16)));
-        dv[mt] = HM_MFMA32(gt, pf[ss], dv[mt]);
-        dk[mt] = HM_MFMA32(qt, df[ss], dk[mt]);
+        bf8_t qt = cat_tr(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ta)),
+                          __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ta + 8 * 16)));
+        bf8_t gt = cat_tr(__builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ta + A::IMG)),
+                          __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(ta + A::IMG + 8 * 16)));
+        dv[mt] = MFMA32(gt, pf[ss], dv[mt]);
+        dk[mt] = MFMA32(qt, df[ss], dk[mt]);
       }
   };
 
@@ -951,7 +924,6 @@ extern "C" int ss_headmajor_pack(const void* src, int in_dtype, const int32_t* g
 // =====================================================================================
 // C-ABI of the head-major window attention (include/scenesplat_hip.h)
 // =====================================================================================
-static inline size_t hm_al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 extern "C" int ss_window_attn_hm_fwd(const void* hm, const int32_t* sidx, const int32_t* win_start, int num_windows,
                                      int max_window, int64_t n, int64_t n_pad, int channels, int num_heads, void* out,
@@ -962,7 +934,7 @@ extern "C" int ss_window_attn_hm_fwd(const void* hm, const int32_t* sidx, const 
 }
 
 extern "C" size_t ss_window_attn_hm_bwd_workspace_bytes(int64_t n, int64_t n_pad, int channels, int num_heads) {
-  return hm_al256((size_t)n_pad * num_heads * 4) + hm_al256((size_t)n_pad * channels * 2) + hm_al256((size_t)(n_pad - n) * 2 * channels * 2);
+  return al256((size_t)n_pad * num_heads * 4) + al256((size_t)n_pad * channels * 2) + al256((size_t)(n_pad - n) * 2 * channels * 2);
 }
 
 extern "C" int ss_window_attn_hm_bwd(const void* hm, const void* out, const void* dout, const float* neg_lse2,
@@ -973,8 +945,8 @@ extern "C" int ss_window_attn_hm_bwd(const void* hm, const void* out, const void
   if (workspace_bytes < ss_window_attn_hm_bwd_workspace_bytes(n, n_pad, channels, num_heads)) return SS_ERR_WORKSPACE;
   if (num_windows == 0) return SS_OK;
   float* ndelta = (float*)workspace;
-  char* doh = (char*)workspace + hm_al256((size_t)n_pad * num_heads * 4);
-  char* extra = doh + hm_al256((size_t)n_pad * channels * 2);
+  char* doh = (char*)workspace + al256((size_t)n_pad * num_heads * 4);
+  char* extra = doh + al256((size_t)n_pad * channels * 2);
   const int inplace = hm_do_inplace(n, channels, max_window);
   int rc = ss_attn_hm_dq(hm, n_pad, dout, out, neg_lse2, ndelta, inplace ? nullptr : doh, sidx, win_start, num_windows, max_window, dqkv,
                          channels, num_heads, scale, stream);

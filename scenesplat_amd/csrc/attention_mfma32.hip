@@ -16,16 +16,11 @@
 //     groups (ds_read_b64_tr_b16 conflict-free);
 //   * staging addresses: per thread three (row, column) pairs fixed before the loop, the window's gather offsets
 //     sit in LDS padded to a multiple of 64 rows: one ds_read + one 64-bit shift-add per 16-byte load.
-#include "attention_internal.h"
+// Operand types, MFMA32, the transposed-read helpers, max3 / swap32 and xcd_remap: attention_frag.h.
+#include "attention_frag.h"
 #include <stdlib.h>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf8_t;
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((ext_vector_type(8))) short s8_t;
-typedef __attribute__((address_space(3))) s4_t lds_s4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;   // native 16-byte vector: staging registers
-
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 #ifndef FA32_THR
 #define FA32_THR 6.0f          // lazy-rescale threshold in exp2 units (P <= 64)
@@ -75,23 +70,6 @@ template <int D> struct A32 {
   static constexpr int KIMG = FA32_BK * KROW, VIMG = FA32_BK * VROW;
 };
 
-__device__ __forceinline__ bf8_t as_bf8_(uint4 v) { return __builtin_bit_cast(bf8_t, v); }
-__device__ __forceinline__ s4_t lds_tr_(const char* addr) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(addr)); }
-__device__ __forceinline__ bf8_t cat_tr_(s4_t lo, s4_t hi) {
-  s8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf8_t, v);
-}
-__device__ __forceinline__ float max3_(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-__device__ __forceinline__ float swap32_(float v) {     // value of lane ^ 32
-  unsigned int u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
-}
-__device__ __forceinline__ int xcd_remap_(int bid, int nb) {
-  int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, slot = bid >> 3;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-}
-
 // issue the 16-byte loads of a K tile (rows rK ..) and a V tile (rows rV ..) into registers; they are written to LDS
 // after the compute phases (global latency hides under the MFMAs)
 template <int NLD>
@@ -133,7 +111,7 @@ k_attn_fwd_mfma32(const unsigned short* __restrict__ qkv, const int32_t* __restr
   if (threadIdx.x == 0 && qchunks < 0) occupancy_pad[0] = 1;
 #endif
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 31, hh = lane >> 5;
-  const int lid = xcd_remap_(blockIdx.x, gridDim.x);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int qc = lid % qchunks; const int t_ = lid / qchunks; const int h = t_ % H; const int w = t_ / H;
   const int p0 = win_start[w], L = win_start[w + 1] - p0;
   const int q0 = qc * FA32_BQ;
@@ -182,7 +160,7 @@ k_attn_fwd_mfma32(const unsigned short* __restrict__ qkv, const int32_t* __restr
       uint4 v = make_uint4(0, 0, 0, 0);
       if (row >= 0 && !(FA32_ABL & 128)) v = *reinterpret_cast<const uint4*>(qkv + row * C3 + h * D + 16 * ks + 8 * hh);
       else if (FA32_ABL & 128) v = make_uint4(0x3c003c00u + lane, 0x3c003c00u, 0x3c003c00u + ks, 0x3c003c00u);
-      qf[qb][ks] = as_bf8_(v);
+      qf[qb][ks] = as_bf8(v);
     }
   }
   // first K / V tile: its row indices come straight from global memory in the same round as the query indices, its rows in
@@ -217,7 +195,7 @@ k_attn_fwd_mfma32(const unsigned short* __restrict__ qkv, const int32_t* __restr
         for (int r = 0; r < 16; ++r) s[qb][blk][r] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < A::NKS; ++ks) {
-        bf8_t a = as_bf8_(*reinterpret_cast<const uint4*>(Kb + koff + blk * 32 * A::KROW + ks * 32));
+        bf8_t a = as_bf8(*reinterpret_cast<const uint4*>(Kb + koff + blk * 32 * A::KROW + ks * 32));
 #pragma unroll
         for (int qb = 0; qb < FA32_NQB; ++qb) s[qb][blk] = MFMA32(a, qf[qb][ks], s[qb][blk]);
       }
@@ -237,14 +215,14 @@ k_attn_fwd_mfma32(const unsigned short* __restrict__ qkv, const int32_t* __restr
   };
   // tile maximum (exp2 units) of the query whose 64 scores sit in lanes lr and lr + 32
   auto tile_max = [&](const f32x16_t (&s)[2]) {
-    float mx = max3_(s[0][0], s[0][1], s[0][2]);
+    float mx = max3(s[0][0], s[0][1], s[0][2]);
 #pragma unroll
-    for (int r = 3; r < 15; r += 2) mx = max3_(mx, s[0][r], s[0][r + 1]);
-    mx = max3_(mx, s[0][15], s[1][0]);
+    for (int r = 3; r < 15; r += 2) mx = max3(mx, s[0][r], s[0][r + 1]);
+    mx = max3(mx, s[0][15], s[1][0]);
 #pragma unroll
-    for (int r = 1; r < 15; r += 2) mx = max3_(mx, s[1][r], s[1][r + 1]);
+    for (int r = 1; r < 15; r += 2) mx = max3(mx, s[1][r], s[1][r + 1]);
     mx = fmaxf(mx, s[1][15]);
-    return fmaxf(mx, swap32_(mx)) * c2;
+    return fmaxf(mx, swap32(mx)) * c2;
   };
   // the running shift moves only past the threshold; then everything accumulated so far is rescaled exactly once
   auto maybe_rescale = [&](int qb, float mx) {
@@ -283,7 +261,7 @@ k_attn_fwd_mfma32(const unsigned short* __restrict__ qkv, const int32_t* __restr
       uint4 pk;
       pk.x = pack_bf16x2(sb[8 * ss + 0], sb[8 * ss + 1]); pk.y = pack_bf16x2(sb[8 * ss + 2], sb[8 * ss + 3]);
       pk.z = pack_bf16x2(sb[8 * ss + 4], sb[8 * ss + 5]); pk.w = pack_bf16x2(sb[8 * ss + 6], sb[8 * ss + 7]);
-      pf[ss] = as_bf8_(pk);
+      pf[ss] = as_bf8(pk);
     }
   };
   // O^T += V^T P^T of one key block for every q-block; element j of lane half hh in step ss <-> key 32 blk + 16 ss + 8 (j>>2)
@@ -299,7 +277,7 @@ k_attn_fwd_mfma32(const unsigned short* __restrict__ qkv, const int32_t* __restr
       const char* vb = Vb + voff + (32 * blk + 16 * ss) * A::VROW;
 #pragma unroll
       for (int mt = 0; mt < A::NMT; ++mt) {
-        bf8_t vf = cat_tr_(lds_tr_(vb + mt * 64), lds_tr_(vb + 8 * A::VROW + mt * 64));
+        bf8_t vf = cat_tr(lds_tr(vb + mt * 64), lds_tr(vb + 8 * A::VROW + mt * 64));
 #pragma unroll
         for (int qb = 0; qb < FA32_NQB; ++qb) o[qb][mt] = MFMA32(vf, pf[qb][ss], o[qb][mt]);
       }
@@ -380,10 +358,10 @@ k_attn_fwd_mfma32(const unsigned short* __restrict__ qkv, const int32_t* __restr
     if (A::PADCOL) {
       // row D of O^T = local row D % 32 of tile D / 32: register ((D%32)>>3)*4 of the hh = ((D%32)>>2)&1 half
       constexpr int LR = D % 32, REG = (LR >> 3) * 4 + (LR & 3), HF = (LR >> 2) & 1;
-      float mine = o[qb][D / 32][REG], other = swap32_(mine);
+      float mine = o[qb][D / 32][REG], other = swap32(mine);
       lt = (hh == HF) ? mine : other;
     } else {
-      lt = lsum[qb] + swap32_(lsum[qb]);
+      lt = lsum[qb] + swap32(lsum[qb]);
     }
     if (qslot[qb] < L) {
       if (hh == 0) lse[(int64_t)(p0 + qslot[qb]) * H + h] = m2[qb] * 0.69314718055994530942f + __logf(lt);

@@ -8,259 +8,18 @@
 // coordinates (three int32 planes, so that the four consecutive keys of an accumulator register quad are one ds_read_b128)
 // and its head's table column in LDS, and adds the three lookups to each score while it sits in the accumulator registers,
 // before the online-softmax maximum.  Indexing, padding and the dqkv / borrowed-slot contract are those of attention_simt.hip
-// and attention_mfma.hip (packed (n, 3C) qkv layout); two kernel pairs:
-//   SIMT  fp32 math on fp32 / bf16 storage: the parity path, any window length
-//   MFMA  v_mfma_f32_16x16x32_bf16, head dims 16/32/48/64, windows up to SS_ATTN_MFMA_MAX_WINDOW; scores and bias in exp2
-//         units (q.k * scale*log2(e) + T*log2(e)), same S^T orientation as attention_mfma.hip
+// and attention_mfma.hip (packed (n, 3C) qkv layout).  This file holds the MFMA kernels: v_mfma_f32_16x16x32_bf16, head dims
+// 16/32/48/64, windows up to SS_ATTN_MFMA_MAX_WINDOW; scores and bias in exp2 units (q.k * scale*log2(e) + T*log2(e)), same
+// S^T orientation, fragment helpers and LDS images as attention_mfma.hip (attention_frag.h); they always take its generic
+// score path (no shift folded into the contraction padding).  The fp32-math parity path for any window length is the RPE
+// instantiation of the kernels in attention_simt.hip; the C-ABI entry points are in attention.hip.
 // Backward: dS = P o (dP - delta), dbias = dS in fp32 (before any rounding to bf16).  dT without global atomics: the dQ
 // kernel accumulates its workgroup's 3 rpe_num bins in LDS (LDS float adds), writes them with plain stores to its slab of the
 // caller's workspace, and k_rpe_dtable_reduce sums the slabs in fixed order into dtable (overwritten; a bin that no pair
 // indexes is exactly 0).
-#include "attention_internal.h"
-#include "../../include/scenesplat_hip.h"
-
-#define RPE_MAX_POS_BND SS_ATTN_RPE_MAX_POS_BND           // 64: int((4 * 8192) ** (1 / 3) * 2)
-#define RPE_MAX_BINS (3 * (2 * RPE_MAX_POS_BND + 1))
-#define RPE_LOG2E 1.44269504088896340736f
+#include "attention_frag.h"
 
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-
-// table index of one axis: qp = query coordinate + pos_bnd (or kc = key coordinate - pos_bnd), result in [0, 2 pos_bnd]
-__device__ __forceinline__ int rpe_bin(int qp_minus_k, int pb2) { return min(max(qp_minus_k, 0), pb2); }
-
-// =====================================================================================
-// SIMT pair (modelled on attention_simt.hip)
-// =====================================================================================
-#define AT_THREADS 256
-#define AT_KT 64
-
-template <typename T, int D>
-__global__ void __launch_bounds__(AT_THREADS)
-k_rpe_fwd_simt(const T* __restrict__ qkv, const int32_t* __restrict__ gidx, const int32_t* __restrict__ sidx,
-               const int32_t* __restrict__ win_start, const int32_t* __restrict__ gc, const float* __restrict__ table,
-               int pos_bnd, T* __restrict__ out, float* __restrict__ lse, int C, int H, float scale) {
-  __shared__ float Ks[AT_KT][D + 1];
-  __shared__ float Vs[AT_KT][D + 1];
-  __shared__ int32_t Cs[AT_KT][3];
-  __shared__ float Ts[RPE_MAX_BINS];
-  const int w = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
-  const int p0 = win_start[w], L = win_start[w + 1] - p0;
-  const int64_t C3 = 3 * (int64_t)C;
-  const int rn = 2 * pos_bnd + 1, pb2 = 2 * pos_bnd;
-  for (int i = tid; i < 3 * rn; i += AT_THREADS) Ts[i] = table[(int64_t)i * H + h];   // visible after the first barrier below
-  for (int qb = 0; qb < L; qb += AT_THREADS) {
-    const int qi = qb + tid;
-    const bool active = qi < L;
-    float q[D], acc[D];
-    float m = -INFINITY, l = 0.f;
-    int qx = 0, qy = 0, qz = 0;
-    if (active) {
-      const int64_t row = gidx[p0 + qi];
-      const T* qp = qkv + row * C3 + h * D;
-#pragma unroll
-      for (int d = 0; d < D; ++d) { q[d] = ElemIO<T>::load(qp + d) * scale; acc[d] = 0.f; }
-      qx = gc[row * 3] + pos_bnd; qy = gc[row * 3 + 1] + pos_bnd; qz = gc[row * 3 + 2] + pos_bnd;
-    }
-    for (int kt = 0; kt < L; kt += AT_KT) {
-      const int nk = min(AT_KT, L - kt);
-      __syncthreads();
-      for (int e = tid; e < nk * D; e += AT_THREADS) {
-        int j = e / D, d = e - j * D;
-        const T* kp = qkv + (int64_t)gidx[p0 + kt + j] * C3 + C + h * D + d;
-        Ks[j][d] = ElemIO<T>::load(kp);
-        Vs[j][d] = ElemIO<T>::load(kp + C);
-      }
-      for (int e = tid; e < nk * 3; e += AT_THREADS) {
-        int j = e / 3, a = e - j * 3;
-        Cs[j][a] = gc[(int64_t)gidx[p0 + kt + j] * 3 + a];
-      }
-      __syncthreads();
-      if (active) {
-        for (int j0 = 0; j0 < nk; j0 += 8) {
-          float s[8], mx = m;
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) {
-            float a = -INFINITY;
-            if (j0 + jj < nk) {
-              const int j = j0 + jj;
-              a = Ts[rpe_bin(qx - Cs[j][0], pb2)] + Ts[rn + rpe_bin(qy - Cs[j][1], pb2)] + Ts[2 * rn + rpe_bin(qz - Cs[j][2], pb2)];
-#pragma unroll
-              for (int d = 0; d < D; ++d) a += q[d] * Ks[j][d];
-            }
-            s[jj] = a; mx = fmaxf(mx, a);
-          }
-          float alpha = __expf(m - mx);
-          l *= alpha;
-#pragma unroll
-          for (int d = 0; d < D; ++d) acc[d] *= alpha;
-#pragma unroll
-          for (int jj = 0; jj < 8; ++jj) {
-            if (j0 + jj < nk) {
-              float p = __expf(s[jj] - mx);
-              l += p;
-#pragma unroll
-              for (int d = 0; d < D; ++d) acc[d] += p * Vs[j0 + jj][d];
-            }
-          }
-          m = mx;
-        }
-      }
-    }
-    if (active) {
-      const int p = p0 + qi;
-      lse[(int64_t)p * H + h] = m + __logf(l);
-      const int32_t row = sidx[p];
-      if (row >= 0) {
-        T* op = out + (int64_t)row * C + h * D;
-        float inv = 1.f / l;
-#pragma unroll
-        for (int d = 0; d < D; ++d) ElemIO<T>::store(op + d, acc[d] * inv);
-      }
-    }
-  }
-}
-
-// dQ and the workgroup's dT bins (slab (window, head, 3 rpe_num), written whole)
-template <typename T, int D>
-__global__ void __launch_bounds__(AT_THREADS)
-k_rpe_bwd_dq_simt(const T* __restrict__ qkv, const T* __restrict__ dout, const float* __restrict__ lse,
-                  const float* __restrict__ delta, const int32_t* __restrict__ gidx, const int32_t* __restrict__ sidx,
-                  const int32_t* __restrict__ win_start, const int32_t* __restrict__ gc, const float* __restrict__ table,
-                  int pos_bnd, T* __restrict__ dqkv, float* __restrict__ slab, int C, int H, float scale) {
-  __shared__ float Ks[AT_KT][D + 1];
-  __shared__ float Vs[AT_KT][D + 1];
-  __shared__ int32_t Cs[AT_KT][3];
-  __shared__ float Ts[RPE_MAX_BINS], Bs[RPE_MAX_BINS];
-  const int w = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
-  const int p0 = win_start[w], L = win_start[w + 1] - p0;
-  const int64_t C3 = 3 * (int64_t)C;
-  const int rn = 2 * pos_bnd + 1, pb2 = 2 * pos_bnd;
-  for (int i = tid; i < 3 * rn; i += AT_THREADS) { Ts[i] = table[(int64_t)i * H + h]; Bs[i] = 0.f; }
-  for (int qb = 0; qb < L; qb += AT_THREADS) {
-    const int qi = qb + tid;
-    const bool active = qi < L;
-    float q[D], go[D], dq[D];
-    float ls = 0.f, dl = 0.f;
-    int qx = 0, qy = 0, qz = 0;
-    int32_t row = -1;
-    if (active) {
-      const int p = p0 + qi;
-      row = sidx[p];
-      const int64_t grow = gidx[p];
-      const T* qp = qkv + grow * C3 + h * D;
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        q[d] = ElemIO<T>::load(qp + d) * scale; dq[d] = 0.f;
-        go[d] = row >= 0 ? ElemIO<T>::load(dout + (int64_t)row * C + h * D + d) : 0.f;
-      }
-      ls = lse[(int64_t)p * H + h]; dl = delta[(int64_t)p * H + h];
-      qx = gc[grow * 3] + pos_bnd; qy = gc[grow * 3 + 1] + pos_bnd; qz = gc[grow * 3 + 2] + pos_bnd;
-    }
-    for (int kt = 0; kt < L; kt += AT_KT) {
-      const int nk = min(AT_KT, L - kt);
-      __syncthreads();
-      for (int e = tid; e < nk * D; e += AT_THREADS) {
-        int j = e / D, d = e - j * D;
-        const T* kp = qkv + (int64_t)gidx[p0 + kt + j] * C3 + C + h * D + d;
-        Ks[j][d] = ElemIO<T>::load(kp);
-        Vs[j][d] = ElemIO<T>::load(kp + C);
-      }
-      for (int e = tid; e < nk * 3; e += AT_THREADS) {
-        int j = e / 3, a = e - j * 3;
-        Cs[j][a] = gc[(int64_t)gidx[p0 + kt + j] * 3 + a];
-      }
-      __syncthreads();
-      if (active && row >= 0) {       // a borrowed query's output is discarded: its dS is 0
-        for (int j = 0; j < nk; ++j) {
-          const int ix = rpe_bin(qx - Cs[j][0], pb2), iy = rn + rpe_bin(qy - Cs[j][1], pb2), iz = 2 * rn + rpe_bin(qz - Cs[j][2], pb2);
-          float s = Ts[ix] + Ts[iy] + Ts[iz], dp = 0.f;
-#pragma unroll
-          for (int d = 0; d < D; ++d) { s += q[d] * Ks[j][d]; dp += go[d] * Vs[j][d]; }
-          float ds = __expf(s - ls) * (dp - dl);
-          atomicAdd(&Bs[ix], ds); atomicAdd(&Bs[iy], ds); atomicAdd(&Bs[iz], ds);
-#pragma unroll
-          for (int d = 0; d < D; ++d) dq[d] += ds * Ks[j][d];
-        }
-      }
-    }
-    if (active && row >= 0) {
-      T* dp_ = dqkv + (int64_t)row * C3 + h * D;
-#pragma unroll
-      for (int d = 0; d < D; ++d) ElemIO<T>::store(dp_ + d, dq[d] * scale);
-    }
-  }
-  __syncthreads();
-  float* my = slab + ((int64_t)w * H + h) * (3 * rn);
-  for (int i = tid; i < 3 * rn; i += AT_THREADS) my[i] = Bs[i];
-}
-
-template <typename T, int D>
-__global__ void __launch_bounds__(AT_THREADS)
-k_rpe_bwd_dkv_simt(const T* __restrict__ qkv, const T* __restrict__ dout, const float* __restrict__ lse,
-                   const float* __restrict__ delta, const int32_t* __restrict__ gidx, const int32_t* __restrict__ sidx,
-                   const int32_t* __restrict__ win_start, const int32_t* __restrict__ gc, const float* __restrict__ table,
-                   int pos_bnd, T* __restrict__ dqkv, T* __restrict__ extra, int C, int H, float scale) {
-  __shared__ float Qs[AT_KT][D + 1];
-  __shared__ float Gs[AT_KT][D + 1];
-  __shared__ float Ls[AT_KT], Dl[AT_KT];
-  __shared__ int32_t Cs[AT_KT][3];
-  __shared__ float Ts[RPE_MAX_BINS];
-  const int w = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
-  const int p0 = win_start[w], L = win_start[w + 1] - p0;
-  const int64_t C3 = 3 * (int64_t)C;
-  const int rn = 2 * pos_bnd + 1, pb2 = 2 * pos_bnd;
-  for (int i = tid; i < 3 * rn; i += AT_THREADS) Ts[i] = table[(int64_t)i * H + h];
-  for (int kb = 0; kb < L; kb += AT_THREADS) {
-    const int kj = kb + tid;
-    const bool active = kj < L;
-    float k[D], v[D], dk[D], dv[D];
-    int kx = 0, ky = 0, kz = 0;       // key coordinate - pos_bnd
-    if (active) {
-      const int64_t grow = gidx[p0 + kj];
-      const T* kp = qkv + grow * C3 + C + h * D;
-#pragma unroll
-      for (int d = 0; d < D; ++d) { k[d] = ElemIO<T>::load(kp + d); v[d] = ElemIO<T>::load(kp + C + d); dk[d] = 0.f; dv[d] = 0.f; }
-      kx = gc[grow * 3] - pos_bnd; ky = gc[grow * 3 + 1] - pos_bnd; kz = gc[grow * 3 + 2] - pos_bnd;
-    }
-    for (int qt = 0; qt < L; qt += AT_KT) {
-      const int nq = min(AT_KT, L - qt);
-      __syncthreads();
-      for (int e = tid; e < nq * D; e += AT_THREADS) {
-        int i = e / D, d = e - i * D;
-        const int p = p0 + qt + i;
-        const int32_t row = sidx[p];
-        Qs[i][d] = ElemIO<T>::load(qkv + (int64_t)gidx[p] * C3 + h * D + d) * scale;
-        Gs[i][d] = row >= 0 ? ElemIO<T>::load(dout + (int64_t)row * C + h * D + d) : 0.f;
-      }
-      for (int e = tid; e < nq * 3; e += AT_THREADS) {
-        int i = e / 3, a = e - i * 3;
-        Cs[i][a] = gc[(int64_t)gidx[p0 + qt + i] * 3 + a];
-      }
-      if (tid < nq) { Ls[tid] = lse[(int64_t)(p0 + qt + tid) * H + h]; Dl[tid] = delta[(int64_t)(p0 + qt + tid) * H + h]; }
-      __syncthreads();
-      if (active) {
-        for (int i = 0; i < nq; ++i) {
-          float s = Ts[rpe_bin(Cs[i][0] - kx, pb2)] + Ts[rn + rpe_bin(Cs[i][1] - ky, pb2)] + Ts[2 * rn + rpe_bin(Cs[i][2] - kz, pb2)];
-          float dp = 0.f;
-#pragma unroll
-          for (int d = 0; d < D; ++d) { s += Qs[i][d] * k[d]; dp += Gs[i][d] * v[d]; }
-          float p = __expf(s - Ls[i]);
-          float ds = p * (dp - Dl[i]);
-#pragma unroll
-          for (int d = 0; d < D; ++d) { dv[d] += p * Gs[i][d]; dk[d] += ds * Qs[i][d]; }  // Qs already carries scale
-        }
-      }
-    }
-    if (active) {
-      const int32_t sr = sidx[p0 + kj];
-      T* dkp; T* dvp;
-      if (sr >= 0) { dkp = dqkv + (int64_t)sr * C3 + C + h * D; dvp = dkp + C; }
-      else { dkp = extra + (int64_t)(-1 - sr) * 2 * C + h * D; dvp = dkp + C; }
-#pragma unroll
-      for (int d = 0; d < D; ++d) { ElemIO<T>::store(dkp + d, dk[d]); ElemIO<T>::store(dvp + d, dv[d]); }
-    }
-  }
-}
 
 // dtable[b][h] = sum over slabs, in fixed order: thread (bx, sy) adds slabs sy, sy + 4, ... and the four partial sums of a
 // bin are added in the order 0..3
@@ -280,69 +39,11 @@ k_rpe_dtable_reduce(const float* __restrict__ slab, int nslab, int H, int nb, fl
   }
 }
 
-// =====================================================================================
-// MFMA pair.  Fragment helpers and LDS images are those of attention_mfma.hip (restated here: that file's kernels stay
-// as they are); the kernels below always take its generic score path (no shift folded into the contraction padding).
-// =====================================================================================
-typedef __attribute__((ext_vector_type(8))) __bf16 bf8_t;
-typedef __attribute__((ext_vector_type(4))) short s4_t;
-typedef __attribute__((ext_vector_type(8))) short s8_t;
-typedef __attribute__((address_space(3))) s4_t lds_s4_t;
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
-template <int D> struct ACfg {
-  static constexpr int DP = (D <= 32) ? 32 : 64;   // padded contraction width of QK^T / dO V^T
-  static constexpr int NKS = DP / 32;              // 32-wide k steps over d
-  static constexpr int NDT = D / 16;               // 16-wide d tiles
-  static constexpr int CH = D / 8;                 // 16-byte chunks per global row
-  static constexpr int CHP = DP / 8;               // 16-byte chunks per padded LDS row
-  static constexpr int ROWB = DP * 2;              // bytes per row of a "row" image
-  static constexpr int TRB = D * 2;                // bytes per row of a "tr" image
-};
-template <int D> __device__ __forceinline__ int row_img_off(int row, int chunk) {   // XOR-swizzled 16-B chunks
-  if (ACfg<D>::DP == 64) return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-  return row * 64 + ((chunk ^ ((3 * (row >> 2)) & 3)) << 4);
-}
-__device__ __forceinline__ bf8_t as_bf8(uint4 v) { return __builtin_bit_cast(bf8_t, v); }
-__device__ __forceinline__ uint4 ld16(const void* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ bf8_t lds_b128(const char* base, int off) { return as_bf8(*reinterpret_cast<const uint4*>(base + off)); }
-// transposed read: lane i of each 16-lane group receives column i of a 4-row x 16-col block
-__device__ __forceinline__ s4_t lds_tr(const char* addr) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(addr)); }
-__device__ __forceinline__ bf8_t cat_tr(s4_t lo, s4_t hi) {
-  s8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf8_t, v);
-}
-__device__ __forceinline__ bf8_t pack8(f32x4_t a, f32x4_t b) {
-  uint4 v;
-  v.x = pack_bf16x2(a[0], a[1]); v.y = pack_bf16x2(a[2], a[3]);
-  v.z = pack_bf16x2(b[0], b[1]); v.w = pack_bf16x2(b[2], b[3]);
-  return as_bf8(v);
-}
-__device__ __forceinline__ float xmax4(float v) {   // over the 4 lane groups (lanes l, l^16, l^32, l^48)
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xsum4(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-__device__ __forceinline__ int xcd_remap(int bid, int nb) {   // bijective: blocks sharing an XCD get adjacent logical ids
-  int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, slot = bid >> 3;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-}
-
-#define FA_NT 2
-#define FA_WAVES 4
-#define FA_THREADS (64 * FA_WAVES)
-#define FA_WQ (16 * FA_NT)            // rows (queries / keys) per wave
-#define FA_BQ (FA_WQ * FA_WAVES)      // 128 rows per workgroup
-#define FA_BK 64
 #define RPE_BIN_WORDS 6208                   // 32 copies of up to 194 bins (pos_bnd <= 31: windows up to 1024), else 16 of up to 387
-#define FA_IDX_CAP SS_ATTN_MFMA_MAX_WINDOW   // a multiple of 64: tiles read the coordinate planes up to the next multiple of 64
 
 // the window in LDS: gather rows as 16-byte offsets (row * 3C/8), the three coordinate planes (zero past the window end up to
-// the next multiple of 64, so that a tile's tail reads are defined), the head's table column in exp2 units
+// the next multiple of 64, so that a tile's tail reads are defined: FA_IDX_CAP is a multiple of 64), the head's table column
+// in exp2 units
 struct RpeWindow {
   int32_t gidx_s[FA_IDX_CAP];
   __attribute__((aligned(16))) int32_t cx[FA_IDX_CAP];
@@ -364,26 +65,6 @@ __device__ __forceinline__ void rpe_window_fill(RpeWindow& W, const int32_t* __r
     W.cx[i] = x; W.cy[i] = y; W.cz[i] = z;
   }
   for (int i = tid; i < 3 * rn; i += nthreads) W.tab[i] = table[(int64_t)i * H + h] * RPE_LOG2E;
-}
-
-// stage a 64-row K/V tile (rows of window slots r0 .. r0+63, clamped to the window's last row) into registers
-template <int D, int NLD>
-__device__ __forceinline__ void tile_load(uint4 (&reg)[NLD], const unsigned short* __restrict__ qkv, const int32_t* gidx_w,
-                                          int r0, int L, int colofs_a, int colofs_b, int tid) {
-  constexpr int CH = ACfg<D>::CH;
-#pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    int c = i * FA_THREADS + tid;
-    int second = c >= 64 * CH;
-    int cc = second ? c - 64 * CH : c;
-    int r = cc / CH, ch = cc - r * CH;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if ((2 * 64 * CH) % FA_THREADS == 0 || c < 2 * 64 * CH) {
-      const uint64_t o16 = (uint32_t)gidx_w[min(r0 + r, L - 1)];
-      v = ld16(reinterpret_cast<const char*>(qkv + (second ? colofs_b : colofs_a) + ch * 8) + (o16 << 4));
-    }
-    reg[i] = v;
-  }
 }
 
 // ---- forward: S^T = K Q^T (key rows 16kt + 4g + r, query lq on the lane), bias added in the accumulators, online softmax
@@ -965,80 +646,17 @@ k_rpe_bwd_dkv_mfma(const unsigned short* __restrict__ qkv, const unsigned short*
 }
 
 // =====================================================================================
-// host side
+// launchers (argument checks and the SIMT / MFMA choice: attention.hip)
 // =====================================================================================
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline int rpe_chunks(int max_window) { return max_window > 0 ? (max_window + FA_BQ - 1) / FA_BQ : 1; }
-static inline bool rpe_head_dim_ok(int d) { return d == 16 || d == 32 || d == 48 || d == 64; }
+static_assert(FA_BQ == SS_ATTN_RPE_BQ, "the workspace holds one dT slab per FA_BQ-query chunk");
 
-// MFMA only where its kernels apply: bf16 rows whose 16-byte offsets fit 32 bits, a window that fits the LDS copy, a head dim
-// of 16/32/48/64; everything else runs on the SIMT pair (which reports the head dims it does not cover)
-static int rpe_pick_impl(int impl, int dtype, int max_window, int64_t n, int channels, int num_heads) {
-  if (impl != SS_ATTN_MFMA) return impl;
-  if (max_window <= 0 || max_window > SS_ATTN_MFMA_MAX_WINDOW || n * (int64_t)(3 * channels / 8) >= (1LL << 31)) return SS_ATTN_SIMT;
-  if (dtype == SS_BF16 && (!rpe_head_dim_ok(channels / num_heads) || (channels & 7))) return SS_ATTN_SIMT;
-  return impl;
-}
-
-static int rpe_args_ok(int num_windows, int channels, int num_heads, int64_t n, int64_t n_pad, int dtype, int pos_bnd) {
-  if (num_windows < 0 || channels <= 0 || num_heads <= 0 || channels % num_heads || n_pad < n) return 0;
-  if (dtype != SS_F32 && dtype != SS_BF16) return 0;
-  return pos_bnd >= 0 && pos_bnd <= RPE_MAX_POS_BND;
-}
-
-template <typename T>
-static int rpe_launch_fwd_simt(const void* qkv, const int32_t* gidx, const int32_t* sidx, const int32_t* ws, int W,
-                               const int32_t* gc, const float* table, int pos_bnd, void* out, float* lse, int C, int H,
-                               float scale, hipStream_t st) {
-  dim3 g(W, H), b(AT_THREADS);
-  const T* q = (const T*)qkv; T* o = (T*)out;
-#define SS_RF_CASE(DD) \
-  case DD: SS_LAUNCH((k_rpe_fwd_simt<T, DD>), g, b, 0, st, q, gidx, sidx, ws, gc, table, pos_bnd, o, lse, C, H, scale); break;
-  switch (C / H) {
-    SS_RF_CASE(16) SS_RF_CASE(32) SS_RF_CASE(48) SS_RF_CASE(64)
-    default: return SS_ERR_ARG;
-  }
-#undef SS_RF_CASE
-  return SS_OK;
-}
-
-template <typename T>
-static int rpe_launch_bwd_simt(const void* qkv, const void* dout, const float* lse, const float* delta, const int32_t* gidx,
-                               const int32_t* sidx, const int32_t* ws, int W, const int32_t* gc, const float* table,
-                               int pos_bnd, void* dqkv, void* extra, float* slab, int C, int H, float scale, hipStream_t st) {
-  dim3 g(W, H), b(AT_THREADS);
-  const T* q = (const T*)qkv; const T* go = (const T*)dout; T* dq = (T*)dqkv; T* ex = (T*)extra;
-#define SS_RB_CASE(DD)                                                                                                        \
-  case DD:                                                                                                                    \
-    SS_LAUNCH((k_rpe_bwd_dq_simt<T, DD>), g, b, 0, st, q, go, lse, delta, gidx, sidx, ws, gc, table, pos_bnd, dq, slab, C, H, scale); \
-    SS_LAUNCH((k_rpe_bwd_dkv_simt<T, DD>), g, b, 0, st, q, go, lse, delta, gidx, sidx, ws, gc, table, pos_bnd, dq, ex, C, H, scale); \
-    break;
-  switch (C / H) {
-    SS_RB_CASE(16) SS_RB_CASE(32) SS_RB_CASE(48) SS_RB_CASE(64)
-    default: return SS_ERR_ARG;
-  }
-#undef SS_RB_CASE
-  return SS_OK;
-}
-
-extern "C" int ss_window_attn_rpe_fwd(const void* qkv, const int32_t* gidx, const int32_t* sidx, const int32_t* win_start,
-                                      int num_windows, int max_window, int64_t n, int64_t n_pad, int channels,
-                                      int num_heads, float scale, int dtype, int impl, const int32_t* grid_coord,
-                                      const float* table, int pos_bnd, void* out, float* lse, hipStream_t stream) {
-  if (!rpe_args_ok(num_windows, channels, num_heads, n, n_pad, dtype, pos_bnd)) return SS_ERR_ARG;
-  if (num_windows == 0) return SS_OK;
-  impl = rpe_pick_impl(impl, dtype, max_window, n, channels, num_heads);
-  const int C = channels, H = num_heads;
-  if (impl == SS_ATTN_SIMT)
-    return dtype == SS_F32
-               ? rpe_launch_fwd_simt<float>(qkv, gidx, sidx, win_start, num_windows, grid_coord, table, pos_bnd, out, lse, C, H, scale, stream)
-               : rpe_launch_fwd_simt<unsigned short>(qkv, gidx, sidx, win_start, num_windows, grid_coord, table, pos_bnd, out, lse, C, H, scale, stream);
-  if (!(impl == SS_ATTN_MFMA && dtype == SS_BF16)) return SS_ERR_ARG;
-  const int qchunks = rpe_chunks(max_window);
-  dim3 g((unsigned)(num_windows * H * qchunks)), b(FA_THREADS);
+int ss_attn_rpe_fwd_mfma(const void* qkv, const int32_t* gidx, const int32_t* sidx, const int32_t* win_start, int W,
+                         int max_window, void* out, float* lse, int C, int H, float scale, const SsAttnRpe& rpe, hipStream_t st) {
+  const int qchunks = ss_attn_rpe_chunks(max_window);
+  dim3 g((unsigned)(W * H * qchunks)), b(FA_THREADS);
   const unsigned short* q = (const unsigned short*)qkv; unsigned short* o = (unsigned short*)out;
 #define SS_RM_CASE(DD) \
-  case DD: SS_LAUNCH((k_rpe_fwd_mfma<DD>), g, b, 0, stream, q, gidx, sidx, win_start, grid_coord, table, pos_bnd, o, lse, C, H, scale, qchunks); break;
+  case DD: SS_LAUNCH((k_rpe_fwd_mfma<DD>), g, b, 0, st, q, gidx, sidx, win_start, rpe.gc, rpe.table, rpe.pos_bnd, o, lse, C, H, scale, qchunks); break;
   switch (C / H) {
     SS_RM_CASE(16) SS_RM_CASE(32) SS_RM_CASE(48) SS_RM_CASE(64)
     default: return SS_ERR_ARG;
@@ -1047,64 +665,30 @@ extern "C" int ss_window_attn_rpe_fwd(const void* qkv, const int32_t* gidx, cons
   return SS_OK;
 }
 
-// delta (n_pad, H) f32 | dK/dV of the borrowed slots | dT slabs ((window, query chunk), head, 3 rpe_num) f32
-extern "C" size_t ss_window_attn_rpe_bwd_workspace_bytes(int64_t n, int64_t n_pad, int channels, int num_heads, int dtype,
-                                                         int num_windows, int max_window, int pos_bnd) {
-  size_t es = dtype == SS_F32 ? 4 : 2;
-  size_t slabs = (size_t)(num_windows > 0 ? num_windows : 0) * rpe_chunks(max_window);
-  return al256((size_t)n_pad * num_heads * 4) + al256((size_t)(n_pad - n) * 2 * channels * es) +
-         al256(slabs * num_heads * 3 * (2 * (size_t)(pos_bnd > 0 ? pos_bnd : 0) + 1) * 4);
+int ss_attn_rpe_bwd_mfma(const void* qkv, const void* dout, const void* out, const float* lse, float* delta, const int32_t* gidx,
+                         const int32_t* sidx, const int32_t* win_start, int W, int max_window, void* dqkv, void* extra,
+                         int C, int H, float scale, const SsAttnRpe& rpe, hipStream_t st) {
+  const int chunks = ss_attn_rpe_chunks(max_window);
+  dim3 g((unsigned)(W * H * chunks)), b(FA_THREADS);
+  const unsigned short* q = (const unsigned short*)qkv; const unsigned short* go = (const unsigned short*)dout;
+  unsigned short* dq = (unsigned short*)dqkv; unsigned short* ex = (unsigned short*)extra;
+#define SS_RMB_CASE(DD)                                                                                                   \
+  case DD:                                                                                                                \
+    SS_LAUNCH((k_rpe_bwd_dq_mfma<DD>), g, b, 0, st, q, go, (const unsigned short*)out, lse, delta, gidx, sidx, win_start, \
+              rpe.gc, rpe.table, rpe.pos_bnd, dq, rpe.slab, C, H, scale, chunks);                                         \
+    SS_LAUNCH((k_rpe_bwd_dkv_mfma<DD>), g, b, 0, st, q, go, lse, (const float*)delta, gidx, sidx, win_start, rpe.gc,      \
+              rpe.table, rpe.pos_bnd, dq, ex, C, H, scale, chunks);                                                       \
+    break;
+  switch (C / H) {
+    SS_RMB_CASE(16) SS_RMB_CASE(32) SS_RMB_CASE(48) SS_RMB_CASE(64)
+    default: return SS_ERR_ARG;
+  }
+#undef SS_RMB_CASE
+  return SS_OK;
 }
 
-extern "C" int ss_window_attn_rpe_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
-                                      const int32_t* gidx, const int32_t* sidx, const int32_t* win_start, int num_windows,
-                                      int max_window, int64_t n, int64_t n_pad, int channels, int num_heads, float scale,
-                                      int dtype, int impl, const int32_t* grid_coord, const float* table, int pos_bnd,
-                                      void* dqkv, float* dtable, void* workspace, size_t workspace_bytes,
-                                      hipStream_t stream) {
-  if (!rpe_args_ok(num_windows, channels, num_heads, n, n_pad, dtype, pos_bnd)) return SS_ERR_ARG;
-  if (workspace_bytes < ss_window_attn_rpe_bwd_workspace_bytes(n, n_pad, channels, num_heads, dtype, num_windows, max_window, pos_bnd))
-    return SS_ERR_WORKSPACE;
-  const int C = channels, H = num_heads, nb = 3 * (2 * pos_bnd + 1);
-  float* delta = (float*)workspace;
-  void* extra = (char*)workspace + al256((size_t)n_pad * H * 4);
-  float* slab = (float*)((char*)extra + al256((size_t)(n_pad - n) * 2 * C * (dtype == SS_F32 ? 4 : 2)));
-  int nslab = 0, rc = SS_OK;
-  if (num_windows > 0) {
-    impl = rpe_pick_impl(impl, dtype, max_window, n, C, H);
-    if (impl == SS_ATTN_SIMT) {
-      rc = ss_attn_delta(out, dout, sidx, delta, n_pad, C, H, dtype, stream);
-      if (rc) return rc;
-      rc = dtype == SS_F32
-               ? rpe_launch_bwd_simt<float>(qkv, dout, lse, delta, gidx, sidx, win_start, num_windows, grid_coord, table, pos_bnd, dqkv, extra, slab, C, H, scale, stream)
-               : rpe_launch_bwd_simt<unsigned short>(qkv, dout, lse, delta, gidx, sidx, win_start, num_windows, grid_coord, table, pos_bnd, dqkv, extra, slab, C, H, scale, stream);
-      if (rc) return rc;
-      nslab = num_windows;
-    } else if (impl == SS_ATTN_MFMA && dtype == SS_BF16) {
-      const int chunks = rpe_chunks(max_window);
-      dim3 g((unsigned)(num_windows * H * chunks)), b(FA_THREADS);
-      const unsigned short* q = (const unsigned short*)qkv; const unsigned short* go = (const unsigned short*)dout;
-      unsigned short* dq = (unsigned short*)dqkv; unsigned short* ex = (unsigned short*)extra;
-#define SS_RMB_CASE(DD)                                                                                                       \
-  case DD:                                                                                                                    \
-    SS_LAUNCH((k_rpe_bwd_dq_mfma<DD>), g, b, 0, stream, q, go, (const unsigned short*)out, lse, delta, gidx, sidx, win_start, \
-              grid_coord, table, pos_bnd, dq, slab, C, H, scale, chunks);                                                     \
-    SS_LAUNCH((k_rpe_bwd_dkv_mfma<DD>), g, b, 0, stream, q, go, lse, (const float*)delta, gidx, sidx, win_start, grid_coord,  \
-              table, pos_bnd, dq, ex, C, H, scale, chunks);                                                                   \
-    break;
-      switch (C / H) {
-        SS_RMB_CASE(16) SS_RMB_CASE(32) SS_RMB_CASE(48) SS_RMB_CASE(64)
-        default: return SS_ERR_ARG;
-      }
-#undef SS_RMB_CASE
-      nslab = num_windows * chunks;
-    } else {
-      return SS_ERR_ARG;
-    }
-    if (n_pad > n) rc = ss_attn_fix_borrowed(gidx, sidx, n_pad, extra, dqkv, C, dtype, stream);
-    if (rc) return rc;
-  }
-  // dtable is overwritten (all zeros when there is no window)
-  SS_LAUNCH(k_rpe_dtable_reduce, dim3((unsigned)ss_div_up((int64_t)H * nb, 64)), dim3(256), 0, stream, (const float*)slab, nslab, H, nb, dtable);
+int ss_attn_rpe_dtable_reduce(const float* slab, int nslab, int H, int pos_bnd, float* dtable, hipStream_t st) {
+  const int nb = 3 * (2 * pos_bnd + 1);
+  SS_LAUNCH(k_rpe_dtable_reduce, dim3((unsigned)ss_div_up((int64_t)H * nb, 64)), dim3(256), 0, st, slab, nslab, H, nb, dtable);
   return SS_OK;
 }

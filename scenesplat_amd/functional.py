@@ -59,8 +59,8 @@ class _WindowAttentionRPE(torch.autograd.Function):
 def window_attention_rpe(qkv, win, grid_coord, table, pos_bnd, num_heads, scale, impl=nv.ATTN_SIMT):
     """window_attention with PTv3's relative position encoding (ptv3:29-48, 199-201): the bias
     table[clamp(g_i - g_j, -pos_bnd, pos_bnd) + pos_bnd] summed over the three axes is added to every score before the softmax,
-    inside the kernels (csrc/attention_rpe.hip).  grid_coord (n, 3) int32 in memory row order; table (3 * (2 * pos_bnd + 1),
-    num_heads).  Gradients: qkv and table."""
+    inside the kernels (MFMA: csrc/attention_rpe.hip; SIMT: the RPE instantiation of csrc/attention_simt.hip).  grid_coord (n, 3)
+    int32 in memory row order; table (3 * (2 * pos_bnd + 1), num_heads).  Gradients: qkv and table."""
     return _WindowAttentionRPE.apply(qkv, table, win, grid_coord, pos_bnd, num_heads, scale, impl)
 
 

@@ -1045,7 +1045,7 @@ def window_attn_bwd(qkv, out, dout, lse, win, num_heads, scale, impl):
     return dqkv
 
 
-# ---- window attention with relative position encoding (csrc/attention_rpe.hip) -----------------
+# ---- window attention with relative position encoding (csrc/attention.hip; kernels: attention_rpe.hip, attention_simt.hip) ----
 def _req_rpe(qkv, win, num_heads, grid_coord, table, pos_bnd):
     n, C3 = qkv.shape
     _req(qkv, None, "qkv")

@@ -113,7 +113,7 @@ def _lin(mod, x):
 
 class RPE(nn.Module):
     """Relative position encoding table of the reference (ptv3:29-48): parameter holder with its key (`rpe_table`), shape and
-    initialisation.  Parameter only: the lookup runs inside the attention kernels (csrc/attention_rpe.hip)."""
+    initialisation.  Parameter only: the lookup runs inside the attention kernels (csrc/attention_rpe.hip, csrc/attention_simt.hip)."""
 
     def __init__(self, patch_size, num_heads):
         super().__init__()

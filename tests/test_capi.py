@@ -1,5 +1,6 @@
 """CPU: the C-ABI library builds/loads and exports every symbol include/scenesplat_hip.h declares
-(no compute calls without a GPU); host-side pure logic."""
+(no compute calls without a GPU); host-side pure logic; the argument contract of the packed-layout attention entry points
+on the paths that return before any launch."""
 import os
 import re
 
@@ -89,3 +90,99 @@ def test_bfs_cluster_host_function_matches_oracle():
     ci, co = po.bfs_cluster(torch.as_tensor(lab), torch.as_tensor(ridx), torch.as_tensor(rsl), 5)
     ri, ro = opo.bfs_cluster(lab, ridx, rsl, 5)
     assert np.array_equal(ci.numpy(), ri) and np.array_equal(co.numpy(), ro) and len(ro) > 2
+
+
+# ---- argument contract of the six packed-layout attention entry points (every call returns before a launch: no GPU) ----
+SS_OK, SS_ERR_ARG, SS_ERR_WORKSPACE = 0, 1, 3
+SS_F32, SS_BF16 = 0, 1
+ATTN_ARGS = dict(num_windows=4, max_window=40, n=150, n_pad=160, channels=64, num_heads=2, dtype=SS_BF16, impl=0, pos_bnd=12,
+                 workspace_bytes=1 << 30)
+BAD_ARGS = [dict(channels=66, num_heads=4), dict(n_pad=149), dict(dtype=2), dict(dtype=-1), dict(num_windows=-1)]
+BAD_RPE_ARGS = [dict(pos_bnd=-1), dict(pos_bnd=65)]
+
+
+def attn_call(lib, name, **over):
+    """one of the four launching entry points with null buffers (never dereferenced on the paths under test)"""
+    a = dict(ATTN_ARGS, **over)
+    head = [a["num_windows"], a["max_window"], a["n"], a["n_pad"], a["channels"], a["num_heads"], 0.125, a["dtype"], a["impl"]]
+    rpe = [None, None, a["pos_bnd"]]
+    if name == "ss_window_attn_fwd":
+        return lib.ss_window_attn_fwd(None, None, None, None, *head, None, None, None)
+    if name == "ss_window_attn_rpe_fwd":
+        return lib.ss_window_attn_rpe_fwd(None, None, None, None, *head, *rpe, None, None, None)
+    if name == "ss_window_attn_bwd":
+        return lib.ss_window_attn_bwd(None, None, None, None, None, None, None, *head, None, None, a["workspace_bytes"], None)
+    assert name == "ss_window_attn_rpe_bwd"
+    return lib.ss_window_attn_rpe_bwd(None, None, None, None, None, None, None, *head, *rpe, None, None, None,
+                                      a["workspace_bytes"], None)
+
+
+def al256(x):
+    return (x + 255) & ~255
+
+
+def plain_workspace(n, n_pad, channels, num_heads, dtype):
+    """delta (n_pad, H) f32 | dK/dV of the borrowed slots (n_pad - n, 2C) in the element type; each part 256-byte aligned"""
+    return al256(n_pad * num_heads * 4) + al256((n_pad - n) * 2 * channels * (4 if dtype == SS_F32 else 2))
+
+
+def rpe_workspace(n, n_pad, channels, num_heads, dtype, num_windows, max_window, pos_bnd):
+    """the plain layout | dT slabs ((window, 128-query chunk), H, 3 * (2 * pos_bnd + 1)) f32"""
+    chunks = (max_window + 127) // 128
+    return plain_workspace(n, n_pad, channels, num_heads, dtype) + al256(num_windows * chunks * num_heads * 3 * (2 * pos_bnd + 1) * 4)
+
+
+ATTN_LAUNCHING = ["ss_window_attn_fwd", "ss_window_attn_bwd", "ss_window_attn_rpe_fwd", "ss_window_attn_rpe_bwd"]
+
+
+@pytest.fixture(scope="module")
+def attn_lib():
+    from scenesplat_amd import _lib, build
+    build.build(verbose=False)
+    return _lib.load()
+
+
+@pytest.mark.parametrize("name", ATTN_LAUNCHING)
+def test_attention_entry_points_refuse_bad_arguments(attn_lib, name):
+    bad = BAD_ARGS + (BAD_RPE_ARGS if "rpe" in name else [])
+    for over in bad:
+        assert attn_call(attn_lib, name, **over) == SS_ERR_ARG, (name, over)
+        if name.endswith("bwd"):      # the argument error wins over a workspace that is too small as well
+            assert attn_call(attn_lib, name, workspace_bytes=0, **over) == SS_ERR_ARG, (name, over)
+    if name == "ss_window_attn_rpe_fwd":      # the ends of the accepted pos_bnd range pass the check
+        for pb in (0, 64):
+            assert attn_call(attn_lib, name, pos_bnd=pb, num_windows=0) == SS_OK
+
+
+def test_attention_backward_refuses_a_short_workspace(attn_lib):
+    a = ATTN_ARGS
+    need = attn_lib.ss_window_attn_bwd_workspace_bytes(a["n"], a["n_pad"], a["channels"], a["num_heads"], a["dtype"])
+    assert attn_call(attn_lib, "ss_window_attn_bwd", workspace_bytes=need - 1) == SS_ERR_WORKSPACE
+    need = attn_lib.ss_window_attn_rpe_bwd_workspace_bytes(a["n"], a["n_pad"], a["channels"], a["num_heads"], a["dtype"],
+                                                           a["num_windows"], a["max_window"], a["pos_bnd"])
+    assert attn_call(attn_lib, "ss_window_attn_rpe_bwd", workspace_bytes=need - 1) == SS_ERR_WORKSPACE
+    for pb in (0, 64):
+        need = attn_lib.ss_window_attn_rpe_bwd_workspace_bytes(a["n"], a["n_pad"], a["channels"], a["num_heads"], a["dtype"],
+                                                               a["num_windows"], a["max_window"], pb)
+        assert attn_call(attn_lib, "ss_window_attn_rpe_bwd", pos_bnd=pb, workspace_bytes=need - 1) == SS_ERR_WORKSPACE
+
+
+def test_attention_without_windows_is_a_no_op(attn_lib):
+    assert attn_call(attn_lib, "ss_window_attn_fwd", num_windows=0) == SS_OK
+    need = attn_lib.ss_window_attn_bwd_workspace_bytes(150, 160, 64, 2, SS_BF16)
+    assert attn_call(attn_lib, "ss_window_attn_bwd", num_windows=0, workspace_bytes=need) == SS_OK
+    assert attn_call(attn_lib, "ss_window_attn_bwd", num_windows=0, workspace_bytes=need - 1) == SS_ERR_WORKSPACE
+
+
+@pytest.mark.parametrize("n,n_pad,channels,num_heads,dtype,num_windows,max_window,pos_bnd", [
+    (360, 400, 64, 2, SS_BF16, 10, 40, 12),          # borrowed slots, a window shorter than one query chunk
+    (1000, 1000, 96, 2, SS_F32, 1, 1000, 31),        # n_pad == n: no borrowed part; 1000 = 7 chunks of 128 + 104
+    (5000, 5120, 192, 4, SS_BF16, 5, 1024, 64),      # the largest pos_bnd
+])
+def test_attention_workspace_sizes_follow_the_stated_layout(attn_lib, n, n_pad, channels, num_heads, dtype, num_windows,
+                                                            max_window, pos_bnd):
+    assert attn_lib.ss_window_attn_bwd_workspace_bytes(n, n_pad, channels, num_heads, dtype) == \
+        plain_workspace(n, n_pad, channels, num_heads, dtype)
+    assert attn_lib.ss_window_attn_rpe_bwd_workspace_bytes(n, n_pad, channels, num_heads, dtype, num_windows, max_window,
+                                                           pos_bnd) == \
+        rpe_workspace(n, n_pad, channels, num_heads, dtype, num_windows, max_window, pos_bnd)

@@ -1,6 +1,7 @@
-"""GPU parity of the relative-position-encoding window attention (csrc/attention_rpe.hip, enable_rpe=True): the kernels
-against the reference module's golden vectors (tests/golden/make_golden_rpe.py), the MFMA pair against the fp32-math SIMT
-pair, a zero table against the bias-free kernels, and the tiny PT-v3m1 with RPE end to end."""
+"""GPU parity of the relative-position-encoding window attention (enable_rpe=True; csrc/attention_rpe.hip and the RPE
+instantiation of csrc/attention_simt.hip): the kernels against the reference module's golden vectors
+(tests/golden/make_golden_rpe.py), the MFMA pair against the fp32-math SIMT pair, a zero table against the bias-free kernels,
+and the tiny PT-v3m1 with RPE end to end."""
 import glob
 import os
 
@@ -155,12 +156,14 @@ def test_window_attention_rpe_mfma_matches_simt_fwd_bwd(H, d, K, counts):
     assert t_s[hit].abs().max() > 0
 
 
+@pytest.mark.parametrize("H,d", [(4, 16), (2, 32), (2, 48), (1, 64)])
 @pytest.mark.parametrize("impl,dtype,tol", IMPLS)
-def test_zero_table_reproduces_plain_window_attention(impl, dtype, tol):
+def test_zero_table_reproduces_plain_window_attention(impl, dtype, tol, H, d):
+    """every head dim of the kernels; on the SIMT path both sides are instantiations of one kernel template"""
     from scenesplat_amd import functional as SF
     from scenesplat_amd.plan import build_plan
     g = torch.Generator().manual_seed(5)
-    counts, H, d, K = [150, 210], 2, 32, 40
+    counts, K = [150, 210], 40
     n, C = sum(counts), H * d
     gc = torch.from_numpy(room(28, 3)[:n])
     plan = build_plan(gc.cuda(), torch.tensor(counts).cumsum(0).cuda(), ORD, ())
