@@ -530,6 +530,24 @@ int ss_ball_grid_query(int m, int nsample, float min_radius, float max_radius, c
 /* neighbour majority vote of the zero-shot evaluator (pointcept/utils/misc.py:17-51): ties -> smallest label, k <= 64 */
 int ss_majority_vote(const int32_t* nn_idx, const int32_t* labels, int64_t m, int k, int ignore_label, int num_classes,
                      int32_t* out, ss_stream_t stream);
+/* ---- open-vocabulary test stage, after the fragment accumulation (csrc/tester.hip) -------------------------------------------
+ * ss_vocab_finish: pointcept/engines/test.py:372-394 in one pass over pred (n, C) f32, 1 <= C <= 256, 1 <= k <= min(C, 8).
+ *   labels (n, k)  the k classes of a row by descending value, equal values: the lower class first (16 lanes per row).  k == 1: a
+ *                  row whose maximum is < threshold (strict) gives ignore_index; k > 1: no threshold (the ScanNet++ top-3 form).
+ *   lut            (C + 1) int32 or NULL: entry 0 = the image of ignore_index, entry c + 1 = the image of class c (pred_label_mapping)
+ *   out (m, k)     out[j, :] = labels[inverse[j], :]; inverse (m) int64 or NULL (m = n, labels are written to out directly).
+ * pred is read once whatever m is; the workspace holds the (n, k) labels when inverse is given.  n == 0 or m == 0: no-op. */
+size_t ss_vocab_finish_workspace_bytes(int64_t n, int k, int64_t m);
+int ss_vocab_finish(const float* pred, int64_t n, int num_classes, int k, float threshold, int32_t ignore_index,
+                    const int64_t* inverse, int64_t m, const int32_t* lut, int32_t* out, void* workspace,
+                    size_t workspace_bytes, ss_stream_t stream);
+/* ss_cluster_vote: clustering_voting (pointcept/utils/misc.py:98-125).  instance_dense[i] in [0, num_instances) or < 0 = no instance
+ * (the row keeps its pred); pred[i] in {ignore_index} U [0, num_classes), num_classes <= 256.  Every row of an instance gets the
+ * instance's most frequent pred value; ignore_index counts as a value like any other, and on equal counts the numerically smallest
+ * value wins (np.unique sorts, argmax takes the first).  Integer counters: exact and reproducible. */
+size_t ss_cluster_vote_workspace_bytes(int num_instances, int num_classes);
+int ss_cluster_vote(const int32_t* pred, const int32_t* instance_dense, int64_t m, int num_instances, int num_classes,
+                    int32_t ignore_index, int32_t* out, void* workspace, size_t workspace_bytes, ss_stream_t stream);
 /* libs/pointgroup_ops/src/bfs_cluster.cpp:140-145.  total (1) device int = number of pairs found */
 int ss_ballquery_batch_p(int n, int mean_active, float radius, const float* xyz, const int32_t* batch_idxs, const int32_t* batch_offsets, int32_t* idx, int32_t* start_len, int32_t* total, ss_stream_t stream);
 /* HOST pointers (CPU BFS, as the reference) */

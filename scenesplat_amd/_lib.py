@@ -164,6 +164,10 @@ PROTOTYPES = {
     "ss_rpe_attn_step2_fwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "ss_rpe_attn_step2_bwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "ss_majority_vote": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_i, c_p, c_p]),
+    "ss_vocab_finish_workspace_bytes": (c_sz, [c_i64, c_i, c_i64]),
+    "ss_vocab_finish": (c_i, [c_p, c_i64, c_i, c_i, c_f, ctypes.c_int32, c_p, c_i64, c_p, c_p, c_p, c_sz, c_p]),
+    "ss_cluster_vote_workspace_bytes": (c_sz, [c_i, c_i]),
+    "ss_cluster_vote": (c_i, [c_p, c_p, c_i64, c_i, c_i, ctypes.c_int32, c_p, c_p, c_sz, c_p]),
     "ss_ballquery_batch_p": (c_i, [c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "ss_bfs_cluster": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p]),
 }

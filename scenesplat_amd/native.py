@@ -859,6 +859,56 @@ def seg_iou(target, num_classes, ignore_index, logits=None, pred=None):
     return out
 
 
+# ---- open-vocabulary test stage: the steps after the accumulation (csrc/tester.hip) ---------------------------------------
+VOCAB_MAX_K = 8
+
+
+def vocab_finish(pred, k=1, threshold=0.0, ignore_index=-1, inverse=None, lut=None):
+    """pred (n, C) f32 -> out (m, k) int32: the k classes of every row by descending value (equal values: the lower class first);
+    k == 1: ignore_index where the maximum is < threshold; lut (C + 1) int32 maps [ignore_index, class 0, ...]; inverse (m) int64
+    expands out[j] = labels[inverse[j]] (engines/test.py:372-394)."""
+    _req(pred, torch.float32, "pred")
+    if pred.dim() != 2 or not 1 <= pred.shape[1] <= SEG_MAX_CLASSES:
+        raise RuntimeError(f"vocab_finish: pred must be (n, C) with 1 <= C <= {SEG_MAX_CLASSES}")
+    n, C = pred.shape
+    k = int(k)
+    if not 1 <= k <= min(C, VOCAB_MAX_K):
+        raise RuntimeError(f"vocab_finish: 1 <= k <= min(C, {VOCAB_MAX_K})")
+    m = n
+    if inverse is not None:
+        _req(inverse, torch.int64, "inverse")
+        if inverse.dim() != 1:
+            raise RuntimeError("inverse: expected a 1-d tensor")
+        m = inverse.shape[0]
+    if lut is not None:
+        _req(lut, torch.int32, "lut", (C + 1,))
+    out = torch.empty((m, k), dtype=torch.int32, device=pred.device)
+    if m == 0:                    # (an empty tensor's pointer is NULL, which the entry point would read as "no inverse")
+        return out
+    if n == 0:
+        raise RuntimeError("vocab_finish: inverse into a pred without rows")
+    ws = _ws(lib().ss_vocab_finish_workspace_bytes(n, k, m), pred.device) if inverse is not None else None
+    check(lib().ss_vocab_finish(_p(pred), n, C, k, float(threshold), int(ignore_index), _p(inverse), m, _p(lut), _p(out), _p(ws),
+                                ws.numel() if ws is not None else 0, _stream()), "ss_vocab_finish")
+    return out
+
+
+def cluster_vote(pred, instance_dense, num_instances, num_classes, ignore_index):
+    """pred (m) int32 in {ignore_index} U [0, C), instance_dense (m) int32 in [0, num_instances) or < 0 -> out (m) int32: every
+    row of an instance takes the instance's most frequent pred (equal counts: the smallest value; utils/misc.py:98-125)."""
+    m = pred.shape[0]
+    _req(pred, torch.int32, "pred", (m,))
+    _req(instance_dense, torch.int32, "instance_dense", (m,))
+    C, ni = int(num_classes), int(num_instances)
+    if not 1 <= C <= SEG_MAX_CLASSES or ni < 0:
+        raise RuntimeError(f"cluster_vote: 1 <= num_classes <= {SEG_MAX_CLASSES}, num_instances >= 0")
+    out = torch.empty(m, dtype=torch.int32, device=pred.device)
+    ws = _ws(lib().ss_cluster_vote_workspace_bytes(ni, C), pred.device)
+    check(lib().ss_cluster_vote(_p(pred), _p(instance_dense), m, ni, C, int(ignore_index), _p(out), _p(ws), ws.numel(), _stream()),
+          "ss_cluster_vote")
+    return out
+
+
 # ---- rows ------------------------------------------------------------------------------------
 def gather_rows(src, idx, out=None):
     """out[i] = src[idx[i]] (zero row where idx < 0).  src (m, C)."""

@@ -1,6 +1,6 @@
 """Host-side mirror of the pointcept interfaces the hot path sits behind (registries,
-``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, ``PDNorm`` / ``PPT-v1m2``, trainer/hook API, the training transforms)."""
-from .registry import HOOKS, LOSSES, MODELS, MODULES, TRAINERS, TRANSFORMS, Registry, build_model  # noqa: F401
+``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, ``PDNorm`` / ``PPT-v1m2``, trainer/hook API, the training transforms, the open-vocabulary tester)."""
+from .registry import HOOKS, LOSSES, MODELS, MODULES, TESTERS, TRAINERS, TRANSFORMS, Registry, build_model  # noqa: F401
 from .structure import Point  # noqa: F401
 from . import ptv3  # noqa: F401  (registers PT-v3m1)
 from . import lang  # noqa: F401  (registers LangPretrainer and the criteria)
@@ -13,3 +13,5 @@ from . import transform  # noqa: F401  (registers the per-sample training transf
 from .transform import Compose  # noqa: F401
 from . import ppt  # noqa: F401  (registers PPT-v1m2)
 from .pdnorm import PDNorm  # noqa: F401  (registered in MODULES)
+from . import tester  # noqa: F401  (registers ZeroShotSemSegTester)
+from .tester import TesterBase, ZeroShotSemSegTester, final_metrics, gather_records, merge_records  # noqa: F401

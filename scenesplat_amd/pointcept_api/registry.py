@@ -79,6 +79,7 @@ LOSSES = Registry("losses")
 HOOKS = Registry("hooks")
 TRAINERS = Registry("trainers")
 TRANSFORMS = Registry("transforms")
+TESTERS = Registry("testers")
 
 
 def build_model(cfg):

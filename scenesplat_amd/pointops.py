@@ -533,3 +533,39 @@ def neighbor_voting(coords, initial_labels, valid_mask, vote_k, ignore_label, nu
     noff = torch.tensor([q.shape[0]], dtype=torch.int32, device=coords.device)
     idx, _ = knn_query(k, vc, off, q, noff)
     return majority_vote(idx, initial_labels[valid], ignore_label, num_classes)
+
+
+def clustering_voting(pred, instance, ignore_index, num_classes):
+    """GPU form of clustering_voting (pointcept/utils/misc.py:98-125): every instance takes its most frequent prediction.
+    ignore_index counts as a value like any other (the reference passes it through np.unique) and equal counts go to the
+    numerically smallest value; rows whose instance id equals ignore_index keep their pred.  pred (m) int in
+    {ignore_index} U [0, num_classes), instance (m) raw ids -> (m) int32."""
+    pred, instance = _i(pred, "pred"), _req(instance.contiguous(), None, "instance")
+    if pred.shape != instance.shape:
+        raise ValueError("clustering_voting: prediction and instance arrays must have the same shape")
+    if pred.numel() == 0:
+        return pred.clone()
+    # once per scene, off the hot path: one fused min / max readback of pred with ignore_index masked out
+    real = pred != int(ignore_index)
+    big = torch.iinfo(torch.int32).max
+    lo_hi = torch.stack([torch.where(real, pred, big).min(), torch.where(real, pred, -big).max()]).tolist()
+    if lo_hi[0] != big and (lo_hi[0] < 0 or lo_hi[1] >= int(num_classes)):
+        raise ValueError(f"clustering_voting: pred outside {{ignore_index}} U [0, {int(num_classes)}): min {lo_hi[0]}, max {lo_hi[1]}")
+    ids, dense = torch.unique(instance, return_inverse=True)
+    hit = ids == int(ignore_index)
+    # the id equal to ignore_index becomes "no instance" (-1); the ids above it move down by one
+    shift = torch.cumsum(hit.to(torch.int64), 0)
+    remap = torch.where(hit, torch.full_like(shift, -1), torch.arange(ids.numel(), device=ids.device) - shift)
+    num_instances = int(ids.numel()) - int(hit.any())
+    return nv.cluster_vote(pred, remap[dense].to(torch.int32).contiguous(), num_instances, int(num_classes), int(ignore_index))
+
+
+def label_map_lut(mapping, num_classes, ignore_index, device=None):
+    """The table ss_vocab_finish applies for `pred_label_mapping` (engines/test.py:392-394): (num_classes + 1) int32, entry 0 the
+    image of ignore_index, entry c + 1 the image of class c.  The (key, item) pairs are applied IN DICT ORDER to an identity
+    table, `lut[lut == key] = item`, which is the reference's sequential in-place loop seen from the domain: chained pairs
+    (a -> b, then b -> c sends a to c) and keys outside the domain behave alike."""
+    lut = torch.cat([torch.tensor([int(ignore_index)]), torch.arange(int(num_classes))]).to(torch.int32)
+    for key, item in (mapping or {}).items():
+        lut[lut == int(key)] = int(item)
+    return lut if device is None else lut.to(device)
