@@ -387,7 +387,9 @@ int ss_feat_text_scan(const void* feat_bf16, const void* text_bf16, int64_t n, i
  *   (torch.nn.CosineSimilarity); mask (n) bytes, non-zero = valid.  target NULL: normalisation only (mask, part,
  *   sums unused).  rowstat (n, 4) f32 is kept for the backward; part = ss_lang_head_blocks(n) * 3 floats of scratch.
  * Backward: coef (2) f32 DEVICE values dL/dsums[0..1]; dp_extra optional gradient arriving at p from other
- *   consumers (the contrastive loss); dfeat (n, C). */
+ *   consumers (the contrastive loss); dfeat (n, C).
+ * n == 0 is a no-op each way (the forward clears sums when given), also with the NULL data pointers of empty tensors;
+ *   the width is checked first. */
 int ss_lang_head_blocks(int64_t n);
 int ss_lang_head_fwd(const void* feat, int feat_dtype, const void* target, int target_dtype, const unsigned char* mask,
                      int normalize, void* p_out, int p_dtype, float* rowstat, float* part, float* sums, int64_t n,

@@ -163,8 +163,8 @@ extern "C" int ss_lang_head_fwd(const void* feat, int feat_dtype, const void* ta
                                 int normalize, void* p_out, int p_dtype, float* rowstat, float* part, float* sums, int64_t n,
                                 int channels, ss_stream_t stream) {
   if (n < 0 || channels <= 0 || channels % 4 || channels > 2048) return SS_ERR_ARG;
+  if (n == 0) { if (sums) hipMemsetAsync(sums, 0, 3 * sizeof(float), stream); return SS_OK; }   // empty tensors have null data
   if (!feat || (target && (!mask || !part || !sums)) || !rowstat) return SS_ERR_ARG;
-  if (n == 0) { if (sums) hipMemsetAsync(sums, 0, 3 * sizeof(float), stream); return SS_OK; }
   const int nb = head_blocks(n), it = (channels + 255) / 256;
 #define HD_FWD(IT) SS_LAUNCH(k_head_fwd<IT>, dim3(nb), dim3(HD_THREADS), 0, stream, feat, feat_dtype, target, target_dtype, mask, \
                              normalize, p_out, p_dtype, rowstat, part, n, channels)
@@ -181,8 +181,8 @@ extern "C" int ss_lang_head_bwd(const void* feat, int feat_dtype, const void* ta
                                 int normalize, const float* rowstat, const float* coef, const void* dp_extra, int dp_dtype,
                                 void* dfeat, int dfeat_dtype, int64_t n, int channels, ss_stream_t stream) {
   if (n < 0 || channels <= 0 || channels % 4 || channels > 2048) return SS_ERR_ARG;
-  if (!feat || !dfeat || !rowstat || (target && (!mask || !coef))) return SS_ERR_ARG;
   if (n == 0) return SS_OK;
+  if (!feat || !dfeat || !rowstat || (target && (!mask || !coef))) return SS_ERR_ARG;
   const int nb = head_blocks(n), it = (channels + 255) / 256;
 #define HD_BWD(IT) SS_LAUNCH(k_head_bwd<IT>, dim3(nb), dim3(HD_THREADS), 0, stream, feat, feat_dtype, target, target_dtype, mask, \
                              normalize, rowstat, coef, dp_extra, dp_dtype, dfeat, dfeat_dtype, n, channels)
