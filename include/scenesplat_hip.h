@@ -22,6 +22,7 @@
  *   ss_seg_iou                                utils/misc.py:167-179 (intersection_and_union_gpu), hooks/evaluator.py:106-240
  *   ss_aug_bbox ... ss_aug_color             pointcept/datasets/transform.py:446-816,1120-1178 (the per-sample augmentations
  *                                             in front of GridSample: CenterShift ... ChromaticJitter)
+ *   ss_voxel_pick_labelled                    pointcept/datasets/transform.py:1245-1253 (GridSample's pick over pc_coord)
  *   ss_knn_query ... ss_bfs_cluster           libs/pointops/src/pointops_api.cpp:15-31,
  *                                             libs/pointops2/src/pointops_api.cpp:17-44,
  *                                             libs/pointgroup_ops/src/bfs_cluster.cpp:140-145
@@ -472,6 +473,12 @@ int ss_aug_elastic(float* coord, int64_t n, const float* noise, int d0, int d1, 
  * bit 2: c <- clip(c + N * jitter_std * 255, 0, 255), N from noise (n,3) or Philox (as above); then normalize != 0: c / 127.5 - 1 */
 int ss_aug_color(float* color, int64_t n, int flags, const float* h_lo, const float* h_hi, float blend, const float* h_tr,
                  float jitter_std, const float* noise, uint64_t seed, int normalize, ss_stream_t stream);
+/* GridSample(apply_to_pc=True) over the point cloud beside the Gaussians (transform.py:1245-1253).  order / idx_ptr: the CSR that
+ * ss_pool_partition wrote over a stable argsort of the cell keys (cell c holds rows order[idx_ptr[c] .. idx_ptr[c+1]), ascending).
+ * chosen[c] = the first of them whose label (int64, indexed by row) differs from ignore_index; the first member when the cell has
+ * none or label is NULL.  n_cells == 0: SS_OK without a launch (pointers are not looked at). */
+int ss_voxel_pick_labelled(const int32_t* order, const int32_t* idx_ptr, int64_t n_cells, const int64_t* label,
+                           int64_t ignore_index, int32_t* chosen, ss_stream_t stream);
 
 /* ---- libs/pointops, pointops2, pointgroup_ops (fp32 features, int32 indices, offset batches) ------- */
 /* libs/pointops/src/knn_query/knn_query_cuda.cpp:7-16; nsample <= 128; idx -1 / dist2 1e10 padding */

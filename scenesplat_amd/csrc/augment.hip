@@ -225,6 +225,26 @@ k_aug_color(float* __restrict__ color, int64_t n, ColorParams P, const float* __
   }
 }
 
+// ---- GridSample over the point cloud beside the Gaussians -----------------------------------------------------------------------
+// One member per occupied cell (pointcept/datasets/transform.py:1245-1253): the first member in sorted order whose label is not
+// ignore_index, the first member when the cell has none or there are no labels.  One thread per cell, grid-stride; the thread walks
+// its run of `order` and writes one int.  No LDS, no atomics: the pick is exact and the same on every run.
+__global__ void __launch_bounds__(AUG_BLOCK)
+k_voxel_pick_labelled(const int32_t* __restrict__ order, const int32_t* __restrict__ idx_ptr, int64_t n_cells,
+                      const int64_t* __restrict__ label, int64_t ignore_index, int32_t* __restrict__ chosen) {
+  for (int64_t c = (int64_t)blockIdx.x * AUG_BLOCK + threadIdx.x; c < n_cells; c += (int64_t)gridDim.x * AUG_BLOCK) {
+    const int32_t lo = idx_ptr[c], hi = idx_ptr[c + 1];
+    int32_t pick = lo < hi ? order[lo] : -1;                        // (a partition has no empty run)
+    if (label) {
+      for (int32_t j = lo; j < hi; ++j) {
+        const int32_t r = order[j];
+        if (label[r] != ignore_index) { pick = r; break; }
+      }
+    }
+    chosen[c] = pick;
+  }
+}
+
 }  // namespace
 
 extern "C" int ss_aug_bbox_blocks(int64_t n) { return aug_blocks(n); }
@@ -291,5 +311,15 @@ extern "C" int ss_aug_color(float* color, int64_t n, int flags, const float* h_l
   P.flags = flags; P.normalize = normalize ? 1 : 0; P.blend = blend; P.jitter_scale = jitter_std * 255.0f; P.seed = seed;
   SS_LAUNCH(k_aug_color, dim3((unsigned)aug_blocks(n)), dim3(AUG_BLOCK), 0, stream, color, n, P,
             (flags & 4) ? noise : (const float*)nullptr);
+  return SS_OK;
+}
+
+extern "C" int ss_voxel_pick_labelled(const int32_t* order, const int32_t* idx_ptr, int64_t n_cells, const int64_t* label,
+                                      int64_t ignore_index, int32_t* chosen, hipStream_t stream) {
+  if (n_cells < 0) return SS_ERR_ARG;
+  if (n_cells == 0) return SS_OK;
+  if (!order || !idx_ptr || !chosen) return SS_ERR_ARG;
+  SS_LAUNCH(k_voxel_pick_labelled, dim3((unsigned)aug_blocks(n_cells)), dim3(AUG_BLOCK), 0, stream, order, idx_ptr, n_cells, label,
+            ignore_index, chosen);
   return SS_OK;
 }

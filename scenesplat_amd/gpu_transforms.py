@@ -10,25 +10,43 @@ import torch
 from . import native as nv
 
 
-@torch.no_grad()
-def grid_sample_train(coord, grid_size, generator=None, return_inverse=False):
-    """coord (N, 3) float GPU tensor -> dict(idx_unique (n,), grid_coord (n, 3) int32 [, inverse (N,)])."""
-    if not coord.is_cuda:
-        raise RuntimeError("grid_sample_train: GPU tensor required (no CPU fallback)")
+def _voxel_keys(coord, grid_size):
+    """-> (gc (N, 3) int64: floor(coord / grid_size) minus its own minimum, key (1, N) int64: the exact packed cell, 21 bits per axis)"""
     gc = torch.floor(coord / grid_size).to(torch.int64)
     gc = gc - gc.amin(0, keepdim=True)
     if int(gc.max()) >= (1 << 21):
         raise ValueError("grid extent exceeds 21 bits per axis")
-    key = ((gc[:, 0] << 42) | (gc[:, 1] << 21) | gc[:, 2]).unsqueeze(0).contiguous()
+    return gc, ((gc[:, 0] << 42) | (gc[:, 1] << 21) | gc[:, 2]).unsqueeze(0).contiguous()
+
+
+@torch.no_grad()
+def grid_sample_train(coord, grid_size, generator=None, return_inverse=False, sampled_index=None, idx_unique=None):
+    """coord (N, 3) float GPU tensor -> dict(idx_unique (n,), grid_coord (n, 3) int32 [, inverse (N,)]).
+    idx_unique replays a recorded per-voxel pick instead of drawing one.  sampled_index (rows that must survive,
+    transform.py:1273-1280): idx_unique becomes unique(idx_unique + sampled_index), ascending, grid_coord follows it, and the
+    dict gains sampled_index = the positions of those rows inside the new idx_unique."""
+    if not coord.is_cuda:
+        raise RuntimeError("grid_sample_train: GPU tensor required (no CPU fallback)")
+    gc, key = _voxel_keys(coord, grid_size)
     order, _, _ = nv.argsort_i64(key, 63, want_inverse=False, want_sorted=False)
     order = order[0]
     cluster, idx_ptr, head, n_out = nv.pool_partition(key[0], order, 0)
     n = int(n_out.item())
     ptr = idx_ptr[:n + 1].long()
     count = ptr[1:] - ptr[:-1]
-    r = torch.randint(0, 1 << 30, (n,), device=coord.device, generator=generator)
-    idx_unique = order[(ptr[:-1] + r % count)].long()          # one random member per voxel (transform.py:1263-1267)
-    out = dict(idx_unique=idx_unique, grid_coord=gc[idx_unique].to(torch.int32), count=count)
+    if idx_unique is None:
+        r = torch.randint(0, 1 << 30, (n,), device=coord.device, generator=generator)
+        idx_unique = order[(ptr[:-1] + r % count)].long()      # one random member per voxel (transform.py:1263-1267)
+    else:
+        idx_unique = idx_unique.to(coord.device, torch.int64)
+    extra = {}
+    if sampled_index is not None:
+        si = sampled_index.to(coord.device, torch.int64).reshape(-1)
+        idx_unique = torch.unique(torch.cat([idx_unique, si]))
+        mask = torch.zeros(coord.shape[0], dtype=torch.bool, device=coord.device)
+        mask[si] = True
+        extra["sampled_index"] = torch.nonzero(mask[idx_unique]).reshape(-1)
+    out = dict(idx_unique=idx_unique, grid_coord=gc[idx_unique].to(torch.int32), count=count, **extra)
     if return_inverse:
         out["inverse"] = cluster.long()
     return out
@@ -44,11 +62,7 @@ def grid_sample_test(coord, grid_size, return_inverse=False):
     reference's numpy argsort leaves the order inside a voxel unspecified)."""
     if not coord.is_cuda:
         raise RuntimeError("grid_sample_test: GPU tensor required (no CPU fallback)")
-    gc = torch.floor(coord / grid_size).to(torch.int64)
-    gc = gc - gc.amin(0, keepdim=True)
-    if int(gc.max()) >= (1 << 21):
-        raise ValueError("grid extent exceeds 21 bits per axis")
-    key = ((gc[:, 0] << 42) | (gc[:, 1] << 21) | gc[:, 2]).unsqueeze(0).contiguous()
+    gc, key = _voxel_keys(coord, grid_size)
     order, _, _ = nv.argsort_i64(key, 63, want_inverse=False, want_sorted=False)
     order = order[0]
     cluster, idx_ptr, head, n_out = nv.pool_partition(key[0], order, 0)
@@ -62,6 +76,33 @@ def grid_sample_test(coord, grid_size, return_inverse=False):
     if return_inverse:
         out["inverse"] = cluster.long()
     return out
+
+
+@torch.no_grad()
+def grid_sample_pc(pc_coord, grid_size, pc_segment=None, ignore_index=-1):
+    """GridSample(apply_to_pc=True) over the point cloud beside the Gaussians (pointcept/datasets/transform.py:1224-1255): one
+    point per occupied cell of the cloud's own grid -- the member with the lowest row index whose pc_segment is not ignore_index,
+    the lowest row index when the cell has none or pc_segment is None (the radix argsort is stable, so a cell's members come in
+    ascending row order: the reference's pick after its stable argsort).  -> chosen (n_cells,) int64 in ascending cell-key order
+    (the reference emits the same rows in the order of its FNV hashes)."""
+    if not isinstance(pc_coord, torch.Tensor) or not pc_coord.is_cuda:
+        raise RuntimeError("grid_sample_pc: GPU tensor required (no CPU fallback)")
+    if pc_coord.dim() != 2 or pc_coord.shape[1] != 3:
+        raise RuntimeError(f"grid_sample_pc: pc_coord must be (m, 3), got {tuple(pc_coord.shape)}")
+    m = pc_coord.shape[0]
+    if pc_segment is not None:
+        if not isinstance(pc_segment, torch.Tensor) or not pc_segment.is_cuda:
+            raise RuntimeError("grid_sample_pc: pc_segment must be a GPU tensor (no CPU fallback)")
+        if pc_segment.reshape(-1).shape[0] != m:
+            raise ValueError(f"grid_sample_pc: pc_segment has {pc_segment.reshape(-1).shape[0]} rows, pc_coord has {m}")
+        pc_segment = pc_segment.reshape(-1).to(torch.int64).contiguous()
+    if m == 0:
+        return torch.empty(0, dtype=torch.int64, device=pc_coord.device)
+    _, key = _voxel_keys(pc_coord, grid_size)            # the cloud's OWN grid, not the Gaussians' (transform.py:1228-1230)
+    order, _, _ = nv.argsort_i64(key, 63, want_inverse=False, want_sorted=False)
+    order = order[0]
+    _, idx_ptr, _, n_out = nv.pool_partition(key[0], order, 0)
+    return nv.voxel_pick_labelled(order, idx_ptr, int(n_out.item()), pc_segment, ignore_index).long()
 
 
 @torch.no_grad()

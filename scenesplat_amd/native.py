@@ -1020,6 +1020,23 @@ def aug_color_(color, flags=0, lo=None, hi=None, blend=0.0, tr=None, jitter_std=
                              _stream()), "ss_aug_color")
 
 
+def voxel_pick_labelled(order, idx_ptr, n_cells, label=None, ignore_index=-1):
+    """chosen (n_cells,) int32: per cell of the CSR (order, idx_ptr) that pool_partition wrote, the first member whose label (int64,
+    per row) is not ignore_index; the first member when the cell has none or label is None."""
+    n_cells = int(n_cells)
+    _req(order, torch.int32, "order"); _req(idx_ptr, torch.int32, "idx_ptr")
+    if n_cells < 0 or idx_ptr.numel() < n_cells + 1:
+        raise RuntimeError("idx_ptr shorter than n_cells + 1")
+    if label is not None:
+        _req(label, torch.int64, "label")
+        if label.dim() != 1 or label.shape[0] < order.numel():
+            raise RuntimeError(f"label: expected one int64 per row of order ({order.numel()}), got {tuple(label.shape)}")
+    chosen = torch.empty(n_cells, dtype=torch.int32, device=order.device)
+    check(lib().ss_voxel_pick_labelled(_p(order), _p(idx_ptr), n_cells, _p(label), int(ignore_index), _p(chosen), _stream()),
+          "ss_voxel_pick_labelled")
+    return chosen
+
+
 def segment_reduce(src, indices, idx_ptr, n_seg, mean):
     _req(src, None, "src"); _req(idx_ptr, torch.int32, "idx_ptr")
     if indices is not None:

@@ -17,6 +17,10 @@ Two things differ from the reference by design:
   arrives.  A run of ChromaticAutoContrast / ChromaticTranslation / ChromaticJitter / NormalizeColor in that order is one
   ``ss_aug_color`` pass.  ``Compose(fuse=False)`` runs op by op.
 
+``pc_coord`` / ``pc_segment`` (the point cloud some val / test lists carry beside the Gaussians) follow the reference: CenterShift, the
+rotations, RandomScale and RandomFlip move the cloud with the Gaussians (a second pending affine, one more ``ss_aug_gaussians`` launch
+per flush), ``GridSample(apply_to_pc=True)`` keeps one point per occupied cell of the cloud's own grid, every other op passes both keys through.
+
 All ops work IN PLACE on float32 contiguous tensors (as the reference mutates its arrays) and refuse CPU tensors: there is no
 CPU fallback.  ``draw``, the host composition (``RigidState`` with a ``bbox_fn``) and ``box_blur3`` need no device.
 """
@@ -98,6 +102,11 @@ def _dev(t, name, cols=None):
     return t
 
 
+def _has_pc(data_dict):
+    """the reference treats pc_coord inside its `if "coord" in data_dict` branches: both keys, or the cloud is left alone"""
+    return "coord" in data_dict and "pc_coord" in data_dict
+
+
 def _noise_arg(noise, like):
     """A recorded (n, 3) N(0,1) array / tensor -> float32 device tensor."""
     if noise is None:
@@ -110,7 +119,10 @@ def _noise_arg(noise, like):
 class RigidState:
     """What a run of rigid ops has folded so far: coord -> A x + b (fp64), quaternion -> q (x) quat then the flip conjugation,
     scale -> scale * smul, normal -> L normal, then the jitter.  bbox_fn(A, b) -> 6 floats overrides the device bounding box
-    (host-only composition: tests, dry runs)."""
+    (host-only composition: tests, dry runs).
+    pc_coord (the point cloud some lists carry beside the Gaussians) -> A_pc x + b_pc: the ops that treat it in the reference
+    (CenterShift, the rotations, RandomScale, RandomFlip) fold into it with `pc=True`, with the Gaussians' shift and centre;
+    RandomShift and RandomJitter do not, so the two affines differ after them.  The flush rules are shared."""
     family = "rigid"
 
     def __init__(self, bbox_fn=None):
@@ -119,6 +131,7 @@ class RigidState:
 
     def reset(self):
         self.A, self.b, self.L = np.eye(3), np.zeros(3), np.eye(3)
+        self.A_pc, self.b_pc = np.eye(3), np.zeros(3)
         self.q = None                 # composed rotation quaternion (wxyz), None = no rotation yet
         self.flip = 0                 # bit 0: x, bit 1: y
         self.smul = np.ones(3)
@@ -130,6 +143,12 @@ class RigidState:
 
     def affine12(self):
         return None if not self.coord_pending() else list(self.A.reshape(-1)) + list(self.b)
+
+    def pc_pending(self):
+        return not (np.array_equal(self.A_pc, np.eye(3)) and not self.b_pc.any())
+
+    def affine12_pc(self):
+        return None if not self.pc_pending() else list(self.A_pc.reshape(-1)) + list(self.b_pc)
 
     def bbox(self, data):
         """Bounding box {min xyz, max xyz} of the current coordinates, pending affine included (6-float readback)."""
@@ -143,11 +162,13 @@ class RigidState:
         if self.jitter is not None:           # the kernel adds the jitter last
             self.flush(data)
 
-    def shift(self, data, t):
+    def shift(self, data, t, pc=False):
         self.before_coord_op(data)
         self.b = self.b + np.asarray(t, dtype=np.float64)
+        if pc:
+            self.b_pc = self.b_pc + np.asarray(t, dtype=np.float64)
 
-    def rotate(self, data, rot, center, has_coord):
+    def rotate(self, data, rot, center, has_coord, pc=False):
         if self.flip or self.jitter is not None:          # the kernel rotates before it flips
             self.flush(data)
         if has_coord:
@@ -157,19 +178,25 @@ class RigidState:
             center = np.asarray(center, dtype=np.float64)
             self.A = rot @ self.A
             self.b = rot @ (self.b - center) + center
+            if pc:                                        # about the SAME centre: the Gaussians' (transform.py:577-580)
+                self.A_pc = rot @ self.A_pc
+                self.b_pc = rot @ (self.b_pc - center) + center
         self.L = rot @ self.L
         r = quat_from_matrix(rot)
         self.q = r if self.q is None else quat_mul(r, self.q)
 
-    def scale(self, data, s):
+    def scale(self, data, s, pc=False):
         self.before_coord_op(data)
         s = np.broadcast_to(np.asarray(s, dtype=np.float64), (3,))
         self.A = s[:, None] * self.A
         self.b = s * self.b
+        if pc:
+            self.A_pc = s[:, None] * self.A_pc
+            self.b_pc = s * self.b_pc
         self.smul = self.smul * s
         self.scaled = True
 
-    def reflect(self, data, flip_x, flip_y):
+    def reflect(self, data, flip_x, flip_y, pc=False):
         if not (flip_x or flip_y):
             return
         if self.flip or self.jitter is not None:          # one conjugation + sign rule per pass
@@ -178,6 +205,9 @@ class RigidState:
         self.A = f[:, None] * self.A
         self.b = f * self.b
         self.L = f[:, None] * self.L
+        if pc:
+            self.A_pc = f[:, None] * self.A_pc
+            self.b_pc = f * self.b_pc
         self.flip = (1 if flip_x else 0) | (2 if flip_y else 0)
 
     def add_jitter(self, data, sigma, clip, seed=0, noise=None):
@@ -186,10 +216,9 @@ class RigidState:
         self.jitter = dict(sigma=sigma, clip=clip, seed=seed, noise=noise)
 
     def flush(self, data):
-        """ONE ss_aug_gaussians pass over the arrays the pending ops touch."""
-        aff = self.affine12()
-        if aff is not None and "pc_coord" in data:
-            raise NotImplementedError("pc_coord (the point cloud beside the Gaussians) has no device form")
+        """ONE ss_aug_gaussians pass over the arrays the pending ops touch, and one more over pc_coord when they touched the cloud."""
+        aff, aff_pc = self.affine12(), self.affine12_pc()
+        pc = _dev(data["pc_coord"], "pc_coord", 3) if aff_pc is not None and "pc_coord" in data else None
         coord = data.get("coord") if (aff is not None or self.jitter is not None) else None
         quat = data.get("quat") if (self.q is not None or self.flip) else None
         scale = data.get("scale") if self.scaled else None
@@ -202,6 +231,8 @@ class RigidState:
                 affine=aff, rquat=None if self.q is None else list(self.q), flip=self.flip, scale_mul=list(self.smul),
                 lin=list(self.L.reshape(-1)), jitter=None if j is None or coord is None else (j["sigma"], j["clip"]),
                 noise=None if j is None or coord is None else _noise_arg(j["noise"], coord), seed=0 if j is None else j["seed"])
+        if pc is not None:
+            nv.aug_gaussians_(coord=pc, affine=aff_pc)
         self.reset()
 
 
@@ -256,7 +287,8 @@ class Transform:
 # ---- rigid family ---------------------------------------------------------------------------------------------------------------
 @TRANSFORMS.register_module()
 class CenterShift(Transform):
-    """transform.py:446-465: x, y to the centre of the bounding box, z to its floor (apply_z) or untouched."""
+    """transform.py:446-465: x, y to the centre of the bounding box, z to its floor (apply_z) or untouched; pc_coord gets the
+    same shift (the Gaussians' box, not its own)."""
     family = "rigid"
 
     def __init__(self, apply_z=True):
@@ -265,7 +297,8 @@ class CenterShift(Transform):
     def fold(self, state, data_dict, params):
         if "coord" in data_dict:
             bb = state.bbox(data_dict)
-            state.shift(data_dict, [-(bb[0] + bb[3]) / 2, -(bb[1] + bb[4]) / 2, -bb[2] if self.apply_z else 0.0])
+            state.shift(data_dict, [-(bb[0] + bb[3]) / 2, -(bb[1] + bb[4]) / 2, -bb[2] if self.apply_z else 0.0],
+                        pc=_has_pc(data_dict))
 
 
 @TRANSFORMS.register_module()
@@ -286,7 +319,7 @@ class RandomShift(Transform):
 @TRANSFORMS.register_module()
 class RandomRotate(Transform):
     """transform.py:544-601: rotates coord about `center` (None: the bounding-box centre of the current coordinates), the
-    Gaussians' quaternions (left-multiplied) and the normals."""
+    Gaussians' quaternions (left-multiplied) and the normals; pc_coord about the same centre."""
     family = "rigid"
 
     def __init__(self, angle=None, center=None, axis="z", always_apply=False, p=0.5):
@@ -304,7 +337,8 @@ class RandomRotate(Transform):
 
     def fold(self, state, data_dict, params):
         if params["fired"]:
-            state.rotate(data_dict, axis_rotation(self.axis, params["angle"]), self.center, "coord" in data_dict)
+            state.rotate(data_dict, axis_rotation(self.axis, params["angle"]), self.center, "coord" in data_dict,
+                         pc=_has_pc(data_dict))
 
 
 @TRANSFORMS.register_module()
@@ -322,7 +356,7 @@ class RandomRotateTargetAngle(RandomRotate):
 
 @TRANSFORMS.register_module()
 class RandomScale(Transform):
-    """transform.py:662-678: coord and the Gaussians' `scale` are multiplied by the same draw."""
+    """transform.py:662-678: coord, pc_coord and the Gaussians' `scale` are multiplied by the same draw."""
     family = "rigid"
 
     def __init__(self, scale=None, anisotropic=False):
@@ -334,12 +368,12 @@ class RandomScale(Transform):
 
     def fold(self, state, data_dict, params):
         if "coord" in data_dict:
-            state.scale(data_dict, params["scale"])
+            state.scale(data_dict, params["scale"], pc=_has_pc(data_dict))
 
 
 @TRANSFORMS.register_module()
 class RandomFlip(Transform):
-    """transform.py:681-727: mirrors x and / or y of coord and normal; the quaternions get the conjugation F R F."""
+    """transform.py:681-727: mirrors x and / or y of coord, pc_coord and normal; the quaternions get the conjugation F R F."""
     family = "rigid"
 
     def __init__(self, p=0.5):
@@ -349,7 +383,7 @@ class RandomFlip(Transform):
         return dict(flip_x=bool(rng.random() < self.p), flip_y=bool(rng.random() < self.p))
 
     def fold(self, state, data_dict, params):
-        state.reflect(data_dict, params["flip_x"], params["flip_y"])
+        state.reflect(data_dict, params["flip_x"], params["flip_y"], pc=_has_pc(data_dict))
 
 
 @TRANSFORMS.register_module()
@@ -560,7 +594,10 @@ class Copy(Transform):
 @TRANSFORMS.register_module()
 class GridSample(Transform):
     """GridSample(mode="train") (transform.py:1181-1300) over gpu_transforms.grid_sample_train: one random point per occupied voxel,
-    `keys` subset to it.  draw() hands the device generator its seed."""
+    `keys` subset to it.  draw() hands the device generator its seed; params["idx"] replays a recorded per-voxel pick.
+    `sampled_index` rows are always kept and remapped (as in RandomDropout).  With apply_to_pc, pc_coord / pc_segment are
+    subset to one point per occupied cell of the cloud's own grid (gpu_transforms.grid_sample_pc), in ascending cell order --
+    the reference emits the same rows in the order of its FNV hashes."""
 
     def __init__(self, grid_size=0.05, hash_type="fnv", mode="train", keys=("coord", "color", "normal", "segment"),
                  return_inverse=False, return_grid_coord=False, return_min_coord=False, return_displacement=False,
@@ -576,17 +613,28 @@ class GridSample(Transform):
         return dict(seed=_seed(rng))
 
     def apply(self, data_dict, params):
-        if "pc_coord" in data_dict and self.apply_to_pc:
-            raise NotImplementedError("GridSample: pc_coord subsampling has no device form")
-        if "sampled_index" in data_dict:
-            raise NotImplementedError("GridSample: sampled_index has no device form")
         coord = data_dict["coord"]
         if not isinstance(coord, torch.Tensor) or not coord.is_cuda:
             raise RuntimeError("GridSample: GPU tensors required (no CPU fallback)")
+        if "pc_coord" in data_dict and self.apply_to_pc:
+            pc = _dev(data_dict["pc_coord"], "pc_coord", 3)
+            seg = data_dict.get("pc_segment")
+            if seg is not None and seg.shape[0] != pc.shape[0]:
+                raise ValueError(f"GridSample: pc_segment has {seg.shape[0]} rows, pc_coord has {pc.shape[0]}")
+            chosen = gt.grid_sample_pc(pc, self.grid_size, seg)
+            data_dict["pc_coord"] = pc[chosen]
+            if seg is not None:
+                data_dict["pc_segment"] = seg[chosen]
         g = torch.Generator(device=coord.device)
         g.manual_seed(int(params.get("seed", 0)))
-        out = gt.grid_sample_train(coord, self.grid_size, generator=g, return_inverse=self.return_inverse)
+        idx = params.get("idx")
+        if idx is not None:
+            idx = torch.as_tensor(np.asarray(idx), dtype=torch.int64).to(coord.device)
+        out = gt.grid_sample_train(coord, self.grid_size, generator=g, return_inverse=self.return_inverse,
+                                   sampled_index=data_dict.get("sampled_index"), idx_unique=idx)
         idx32 = out["idx_unique"].to(torch.int32).contiguous()
+        if "sampled_index" in out:
+            data_dict["sampled_index"] = out["sampled_index"]
         if self.return_inverse:
             data_dict["inverse"] = out["inverse"]
         if self.return_grid_coord:

@@ -11,6 +11,12 @@ timed on a synthetic SceneSplat-like sample at n = 200,000 and n = 800,000 Gauss
            rows in the 256 MiB Infinity Cache; median over the windows, and the bytes the algorithm moves (coord 12, quat 16,
            scale 12, normal 12, colour 12 bytes per row, read and written where updated) over that time as a share of the 8 TB/s peak.
 
+  --cloud  the point cloud beside the Gaussians (pc_coord / pc_segment): m = 1,000,000 points beside 1,000,000 Gaussians, grid 0.02.
+           The cloud's rigid pass (ss_aug_gaussians on pc_coord alone, HBM-resident as under `kernels`), gpu_transforms.grid_sample_pc
+           as a call and split into key build, sort, partition and pick (--cloud-iters back-to-back calls between one event pair,
+           median over the windows), and the same pick written with torch ops (gather, compare, where, scatter_reduce, modulo) on
+           the same partition, checked to give the same rows.
+
 The CPU chain of the reference is not timed here.  Needs a GPU: there is no CPU path.  Prints markdown tables and one JSON line."""
 import argparse
 import json
@@ -127,8 +133,73 @@ def time_kernels(n, dev, iters, repeats, resident_mib):
     return out, sets
 
 
+def time_cloud(m, n, grid, dev, iters, repeats, resident_mib):
+    """-> {name: dict(us=[per call, one per window], note)} for the cloud of m points beside n Gaussians"""
+    from scenesplat_amd import gpu_transforms as gt, native as nv
+    g = torch.Generator(device=dev).manual_seed(11)
+    box = torch.tensor([8.0, 6.0, 3.0], device=dev)
+    sets = max(2, -(-resident_mib * (1 << 20) // (12 * m)))
+    clouds = [torch.rand(m, 3, device=dev, generator=g) * box for _ in range(sets)]
+    pc = clouds[0]
+    seg = torch.randint(-1, 20, (m,), device=dev, generator=g)
+    gauss = sample(n, dev)["coord"]                                   # the Gaussians the cloud lies beside: allocated, as in a real call
+    aff = [1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0, 0.0, 0.0, 0.0]
+    key = gt._voxel_keys(pc, grid)[1]
+    order = nv.argsort_i64(key, 63, want_inverse=False, want_sorted=False)[0][0]
+    cluster, idx_ptr, _, n_out = nv.pool_partition(key[0], order, 0)
+    n_cells = int(n_out.item())
+
+    def torch_pick():
+        o = order.long()
+        cell = cluster.long()[o]                                      # the cell of every sorted position
+        lab = seg[o]
+        pos = torch.arange(m, device=dev)
+        cand = torch.where(lab != -1, pos, pos + m)                   # labelled members sort in front of the others
+        best = torch.full((n_cells,), 2 * m, dtype=torch.int64, device=dev).scatter_reduce(0, cell, cand, "amin")
+        return o[best % m]
+    want = nv.voxel_pick_labelled(order, idx_ptr, n_cells, seg, -1).long()
+    assert torch.equal(want, torch_pick()) and torch.equal(want, gt.grid_sample_pc(pc, grid, seg))
+    turn = [0]
+
+    def rigid():
+        turn[0] += 1
+        nv.aug_gaussians_(coord=clouds[turn[0] % sets], affine=aff)
+    cases = {
+        "rigid pass over the cloud (ss_aug_gaussians, coord only), %d copies" % sets: rigid,
+        "grid_sample_pc, whole call (one n_cells readback)": lambda: gt.grid_sample_pc(pc, grid, seg),
+        "  keys (floor, min, pack: torch)": lambda: gt._voxel_keys(pc, grid),
+        "  sort (ss_argsort_i64, 63 bits)": lambda: nv.argsort_i64(key, 63, want_inverse=False, want_sorted=False),
+        "  partition (ss_pool_partition)": lambda: nv.pool_partition(key[0], order, 0),
+        "  pick (ss_voxel_pick_labelled)": lambda: nv.voxel_pick_labelled(order, idx_ptr, n_cells, seg, -1),
+        "  pick, no labels": lambda: nv.voxel_pick_labelled(order, idx_ptr, n_cells, None, -1),
+        "the same pick in torch ops (gather x3, compare, where, scatter_reduce, modulo)": torch_pick,
+    }
+    out = {}
+    for name, fn in cases.items():
+        for _ in range(5):
+            fn()
+        us = []
+        for _ in range(repeats):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            us.append(a.elapsed_time(b) * 1e3 / iters)
+        out[name] = dict(us=us)
+    del gauss
+    return out, n_cells
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cloud", action="store_true", help="time the point cloud beside the Gaussians instead of the chain")
+    ap.add_argument("--cloud-points", type=int, default=1000000)
+    ap.add_argument("--cloud-gaussians", type=int, default=1000000)
+    ap.add_argument("--cloud-grid", type=float, default=0.02)
+    ap.add_argument("--cloud-iters", type=int, default=200, help="back-to-back calls per cloud timing window")
     ap.add_argument("--sizes", type=int, nargs="+", default=[200000, 800000])
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=15)
@@ -138,6 +209,17 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_augment.py needs a GPU: the transforms have no CPU path")
     dev = torch.device("cuda")
+    if args.cloud:
+        m, n = args.cloud_points, args.cloud_gaussians
+        res, n_cells = time_cloud(m, n, args.cloud_grid, dev, args.cloud_iters, max(3, args.repeats // 3), args.resident_mib)
+        print(f"\n## cloud of m = {m:,} points beside {n:,} Gaussians, grid {args.cloud_grid}: {n_cells:,} occupied cells "
+              f"({args.cloud_iters} calls per window)\n")
+        print("| step | us per call: median | min - max |")
+        print("|---|---|---|")
+        for name, k in res.items():
+            print(f"| {name} | {median(k['us']):.1f} | {min(k['us']):.1f} - {max(k['us']):.1f} |")
+        print(json.dumps(dict(cloud=dict(m=m, n=n, grid=args.cloud_grid, n_cells=n_cells, steps=res))))
+        return
     result = {}
     for n in args.sizes:
         ms = time_chain(n, dev, args.warmup, args.repeats)
