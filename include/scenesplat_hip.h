@@ -23,6 +23,8 @@
  *   ss_aug_bbox ... ss_aug_color             pointcept/datasets/transform.py:446-816,1120-1178 (the per-sample augmentations
  *                                             in front of GridSample: CenterShift ... ChromaticJitter)
  *   ss_voxel_pick_labelled                    pointcept/datasets/transform.py:1245-1253 (GridSample's pick over pc_coord)
+ *   ss_color_chain / ss_voxel_blur            pointcept/datasets/transform.py:820-1032 (RandomColorJitter, RandomColorGrayScale),
+ *                                             :60-176 (GSGaussianBlurVoxelOpc)
  *   ss_knn_query ... ss_bfs_cluster           libs/pointops/src/pointops_api.cpp:15-31,
  *                                             libs/pointops2/src/pointops_api.cpp:17-44,
  *                                             libs/pointgroup_ops/src/bfs_cluster.cpp:140-145
@@ -479,6 +481,35 @@ int ss_aug_color(float* color, int64_t n, int flags, const float* h_lo, const fl
  * none or label is NULL.  n_cells == 0: SS_OK without a launch (pointers are not looked at). */
 int ss_voxel_pick_labelled(const int32_t* order, const int32_t* idx_ptr, int64_t n_cells, const int64_t* label,
                            int64_t ignore_index, int32_t* chosen, ss_stream_t stream);
+
+/* ---- the self-supervised view generator's colour and blur transforms (csrc/ssl_views.hip) -----------------------------------------
+ * RandomColorJitter / RandomColorGrayScale (transform.py:820-1032) as ONE pass over color (n,3), fp32 on the 0..255 scale, in place.
+ * h_codes / h_factors: num_steps <= 8 HOST (code, factor) pairs applied per point in the given order:
+ *   1 brightness  c <- clip(f c, 0, 255)
+ *   2 contrast    c <- clip(f c + (1 - f) mean, 0, 255), mean = the mean over all n points of 0.2989 r + 0.587 g + 0.114 b of the colours
+ *                 as they are when the step is reached
+ *   3 saturation  the same blend against the point's own gray
+ *   4 hue         rgb / 255 -> hsv (ties: maxc == r, then maxc == g), h <- (h + f) mod 1 (non-negative), hsv -> rgb * 255; p, q, t are
+ *                 clipped to [0, 1], v and the result are not; -0.5 <= f <= 0.5; evaluated in fp64 as the reference's promotion has it
+ *   5 grayscale   r, g, b <- gray (the factor is ignored)
+ * Each contrast step costs one reduction pass that re-applies the steps in front of it in registers and writes nothing to color: per-block
+ * partials (ss_color_chain_blocks(n) floats) and a one-wave fp64 finish, no atomics, the same bits on every run.  The means stay in
+ * `means` (8 floats, device; slot k belongs to step k) for the apply pass: no readback.  partials / means may be NULL without a contrast step. */
+int ss_color_chain_blocks(int64_t n);
+int ss_color_chain(float* color, int64_t n, int num_steps, const int* h_codes, const float* h_factors, float* partials, float* means,
+                   ss_stream_t stream);
+/* GSGaussianBlurVoxelOpc (transform.py:60-176) without the dense grid.  grid_coord (n,3) int32, unique rows, any origin; mask (n) bytes
+ * (NULL = every row).  The masked voxels go into an open-addressing hash (ss_voxel_blur_table_size(n) slots >= 2 n); every masked row then
+ * sums w(dx) w(dy) w(dz) * value and w(dx) w(dy) w(dz) over the (2r+1)^3 neighbours that are masked voxels, r = int(2 sigma + 0.5) <= 8,
+ * w(x) = exp(-x^2 / 2 sigma^2) / sum w (scipy's kernel at truncate = 2.0), indices outside [0, size) folded back by scipy's `reflect` rule
+ * with size = max - min + 1 of grid_coord over ALL rows (a device reduction), and is overwritten by sum / (wsum + 1e-7), accumulated in
+ * fp64.  color (n,3) always; opacity (n,1), scale (n,3), quat (n,4), normal (n,3) when not NULL.  normalize_quat != 0: afterwards EVERY
+ * row of quat is divided by its norm (rows of zero norm are left as they are).  No readback, O(n) workspace; its int32 word 6 is a status
+ * the caller may look at: != 0 when an axis spans 2^21 cells or more, in which case nothing was blurred. */
+int64_t ss_voxel_blur_table_size(int64_t n);
+size_t ss_voxel_blur_workspace_bytes(int64_t n);
+int ss_voxel_blur(const int32_t* grid_coord, const uint8_t* mask, int64_t n, float* color, float* opacity, float* scale, float* quat,
+                  float* normal, int normalize_quat, float sigma, void* workspace, size_t workspace_bytes, ss_stream_t stream);
 
 /* ---- libs/pointops, pointops2, pointgroup_ops (fp32 features, int32 indices, offset batches) ------- */
 /* libs/pointops/src/knn_query/knn_query_cuda.cpp:7-16; nsample <= 128; idx -1 / dist2 1e10 padding */

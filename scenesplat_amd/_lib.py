@@ -137,6 +137,11 @@ PROTOTYPES = {
     "ss_aug_elastic": (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_p, c_f, c_f, c_p]),
     "ss_aug_color": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_f, c_p, c_f, c_p, ctypes.c_uint64, c_i, c_p]),
     "ss_voxel_pick_labelled": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
+    "ss_color_chain_blocks": (c_i, [c_i64]),
+    "ss_color_chain": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "ss_voxel_blur_table_size": (c_i64, [c_i64]),
+    "ss_voxel_blur_workspace_bytes": (c_sz, [c_i64]),
+    "ss_voxel_blur": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_sz, c_p]),
     "ss_knn_grid_table_size": (c_i64, [c_i64]),
     "ss_knn_grid_workspace_bytes": (c_sz, [c_i64]),
     "ss_knn_grid_keys": (c_i, [c_p, c_p, c_i, c_i64, c_f, c_f, c_f, c_f, c_p, c_p]),

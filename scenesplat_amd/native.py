@@ -1020,6 +1020,60 @@ def aug_color_(color, flags=0, lo=None, hi=None, blend=0.0, tr=None, jitter_std=
                              _stream()), "ss_aug_color")
 
 
+# ---- the SSL view generator's colour chain and sparse voxel blur (csrc/ssl_views.hip) --------
+CHAIN_BRIGHTNESS, CHAIN_CONTRAST, CHAIN_SATURATION, CHAIN_HUE, CHAIN_GRAY = 1, 2, 3, 4, 5
+CHAIN_MAX_STEPS = 8
+
+
+def color_chain_(color, steps):
+    """steps = [(code, factor), ...] (at most 8) on color (n, 3), 0..255, in place and in ONE pass, plus one reduction pass per
+    contrast step (its mean gray stays on the device).  See include/scenesplat_hip.h for the formulas."""
+    _rows3(color, "color")
+    steps = [(int(c), float(f)) for c, f in steps]
+    if len(steps) > CHAIN_MAX_STEPS:
+        raise RuntimeError(f"color_chain_: at most {CHAIN_MAX_STEPS} steps, got {len(steps)}")
+    n = color.shape[0]
+    if not steps or n == 0:
+        return color
+    part = means = None
+    if any(c == CHAIN_CONTRAST for c, _ in steps):
+        part = torch.empty(lib().ss_color_chain_blocks(n), dtype=torch.float32, device=color.device)
+        means = torch.empty(CHAIN_MAX_STEPS, dtype=torch.float32, device=color.device)
+    codes = (ctypes.c_int * len(steps))(*[c for c, _ in steps])
+    check(lib().ss_color_chain(_p(color), n, len(steps), codes, _hf([f for _, f in steps], len(steps), "factors"), _p(part), _p(means),
+                               _stream()), "ss_color_chain")
+    return color
+
+
+def voxel_blur_(grid_coord, mask, color, sigma, opacity=None, scale=None, quat=None, normal=None, normalize_quat=False):
+    """GSGaussianBlurVoxelOpc's blur over the occupied voxels only, in place on the rows where mask (n,) bool is set (None: all):
+    color and the optional opacity (n, 1) / scale / quat / normal become the Gaussian-weighted mean over the masked voxels of
+    their (2r+1)^3 neighbourhood; normalize_quat then divides EVERY row of quat by its norm.  grid_coord (n, 3) int32 with unique
+    rows.  -> the device int32 status word (0 = done; 1 = an axis spans 2^21 cells or more and nothing was blurred); reading it
+    is a sync the caller may or may not want."""
+    _req(grid_coord, torch.int32, "grid_coord")
+    n = grid_coord.shape[0]
+    if grid_coord.dim() != 2 or grid_coord.shape[1] != 3:
+        raise RuntimeError(f"grid_coord: expected (n, 3), got {tuple(grid_coord.shape)}")
+    _rows3(color, "color")
+    for t, name, cols in ((opacity, "opacity", 1), (scale, "scale", 3), (quat, "quat", 4), (normal, "normal", 3)):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if t.numel() != n * cols or (t.dim() == 2 and t.shape[1] != cols):
+                raise RuntimeError(f"{name}: expected (n, {cols}) with n = {n}, got {tuple(t.shape)}")
+    if color.shape[0] != n:
+        raise RuntimeError(f"color: {color.shape[0]} rows, grid_coord has {n}")
+    if mask is not None:
+        _req(mask, None, "mask", (n,))
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError(f"mask: expected bool or uint8, got {mask.dtype}")
+    nbytes = lib().ss_voxel_blur_workspace_bytes(n)
+    ws = _ws(nbytes, grid_coord.device)
+    check(lib().ss_voxel_blur(_p(grid_coord), _p(mask), n, _p(color), _p(opacity), _p(scale), _p(quat), _p(normal),
+                              int(bool(normalize_quat)), float(sigma), _p(ws), ws.numel(), _stream()), "ss_voxel_blur")
+    return ws[24:28].view(torch.int32)
+
+
 def voxel_pick_labelled(order, idx_ptr, n_cells, label=None, ignore_index=-1):
     """chosen (n_cells,) int32: per cell of the CSR (order, idx_ptr) that pool_partition wrote, the first member whose label (int64,
     per row) is not ignore_index; the first member when the cell has none or label is None."""

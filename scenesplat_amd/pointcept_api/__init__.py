@@ -11,6 +11,8 @@ from . import seg  # noqa: F401  (registers DefaultSegmentorV2, CrossEntropyLoss
 from .engine import HookBase, Trainer, TrainerBase, create_ddp_model  # noqa: F401
 from . import transform  # noqa: F401  (registers the per-sample training transforms)
 from .transform import Compose  # noqa: F401
+from .transform import (CollectContrast, ContrastiveViewsGenerator_SSL, GSGaussianBlurVoxelOpc, RandomColorGrayScale,  # noqa: F401
+                        RandomColorJitter, RandomColorSolarize, SphereCropRandomMaxPoints)   # (the self-supervised view generator)
 from . import ppt  # noqa: F401  (registers PPT-v1m2)
 from .pdnorm import PDNorm  # noqa: F401  (registered in MODULES)
 from . import tester  # noqa: F401  (registers ZeroShotSemSegTester)

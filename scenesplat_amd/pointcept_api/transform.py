@@ -15,7 +15,8 @@ Two things differ from the reference by design:
   device -> host readback (a sync) per such op, and no pass over memory is spent on flushing.  The pass is flushed at the first
   op outside the family, when a rotation follows a flip or a jitter (the kernel rotates first), or when a second flip or jitter
   arrives.  A run of ChromaticAutoContrast / ChromaticTranslation / ChromaticJitter / NormalizeColor in that order is one
-  ``ss_aug_color`` pass.  ``Compose(fuse=False)`` runs op by op.
+  ``ss_aug_color`` pass.  RandomColorJitter / RandomColorGrayScale (the self-supervised view lists) are a family of their own:
+  their fired steps queue up, in any order, for ONE ``ss_color_chain`` pass.  ``Compose(fuse=False)`` runs op by op.
 
 ``pc_coord`` / ``pc_segment`` (the point cloud some val / test lists carry beside the Gaussians) follow the reference: CenterShift, the
 rotations, RandomScale and RandomFlip move the cloud with the Gaussians (a second pending affine, one more ``ss_aug_gaussians`` launch
@@ -24,6 +25,9 @@ per flush), ``GridSample(apply_to_pc=True)`` keeps one point per occupied cell o
 All ops work IN PLACE on float32 contiguous tensors (as the reference mutates its arrays) and refuse CPU tensors: there is no
 CPU fallback.  ``draw``, the host composition (``RigidState`` with a ``bbox_fn``) and ``box_blur3`` need no device.
 """
+import copy
+import numbers
+
 import numpy as np
 import torch
 
@@ -261,7 +265,26 @@ class ColorState:
         self.reset()
 
 
-_STATES = dict(rigid=RigidState, color=ColorState)
+class ChainState:
+    """Pending (code, factor) steps of RandomColorJitter / RandomColorGrayScale, in the order they were drawn: one ss_color_chain
+    pass at the flush (plus one reduction pass per contrast step).  The kernel takes 8 steps; a ninth flushes first."""
+    family = "chain"
+
+    def __init__(self):
+        self.steps = []
+
+    def add(self, data, code, factor=0.0):
+        if len(self.steps) == nv.CHAIN_MAX_STEPS:
+            self.flush(data)
+        self.steps.append((code, float(factor)))
+
+    def flush(self, data):
+        if self.steps and "color" in data:
+            nv.color_chain_(_dev(data["color"], "color", 3), self.steps)
+        self.steps = []
+
+
+_STATES = dict(rigid=RigidState, color=ColorState, chain=ChainState)
 
 
 class Transform:
@@ -583,7 +606,6 @@ class Copy(Transform):
         self.keys_dict = dict(coord="origin_coord", segment="origin_segment") if keys_dict is None else keys_dict
 
     def apply(self, data_dict, params):
-        import copy
         for key, value in self.keys_dict.items():
             if key in data_dict:
                 v = data_dict[key]
@@ -674,6 +696,245 @@ class Collect(Transform):
         return gt.collect(data_dict, self.keys, self.offset_keys, **self.kwargs)
 
 
+# ---- the self-supervised view generator (transform.py:18-315, 820-1032) ---------------------------------------------------------
+@TRANSFORMS.register_module()
+class RandomColorGrayScale(Transform):
+    """transform.py:819-848: with probability p all three channels become 0.2989 r + 0.587 g + 0.114 b."""
+    family = "chain"
+
+    def __init__(self, p):
+        self.p = p
+
+    def draw(self, rng, data_dict):
+        return dict(fired=bool(rng.random() < self.p))
+
+    def fold(self, state, data_dict, params):
+        if params["fired"] and "color" in data_dict:
+            state.add(data_dict, nv.CHAIN_GRAY)
+
+
+@TRANSFORMS.register_module()
+class RandomColorJitter(Transform):
+    """transform.py:851-1032 (after torchvision): brightness / contrast / saturation / hue in a drawn order, each applied with
+    probability p.  draw() -> order (a permutation of 0..3 = brightness, contrast, saturation, hue) and the four factors; a factor
+    is None when its range is None or its own `rand() < p` did not fire -- only steps that have a range consume a p draw, as in
+    the reference's __call__.  The fired steps are ONE ss_color_chain pass (and fold into the pass of a neighbouring
+    RandomColorGrayScale under Compose(fuse=True))."""
+    family = "chain"
+    NAMES = ("brightness", "contrast", "saturation", "hue")
+    CODES = (nv.CHAIN_BRIGHTNESS, nv.CHAIN_CONTRAST, nv.CHAIN_SATURATION, nv.CHAIN_HUE)
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, p=0.95):
+        self.brightness = self._check_input(brightness, "brightness")
+        self.contrast = self._check_input(contrast, "contrast")
+        self.saturation = self._check_input(saturation, "saturation")
+        self.hue = self._check_input(hue, "hue", center=0, bound=(-0.5, 0.5), clip_first_on_zero=False)
+        self.p = p
+
+    @staticmethod
+    def _check_input(value, name, center=1, bound=(0, float("inf")), clip_first_on_zero=True):
+        if isinstance(value, numbers.Number):
+            if value < 0:
+                raise ValueError("If {} is a single number, it must be non negative.".format(name))
+            value = [center - float(value), center + float(value)]
+            if clip_first_on_zero:
+                value[0] = max(value[0], 0.0)
+        elif isinstance(value, (tuple, list)) and len(value) == 2:
+            if not bound[0] <= value[0] <= value[1] <= bound[1]:
+                raise ValueError("{} values should be between {}".format(name, bound))
+        else:
+            raise TypeError("{} should be a single number or a list/tuple with length 2.".format(name))
+        if value[0] == value[1] == center:      # 0 or (1, 1) for brightness / contrast / saturation, (0, 0) for hue: nothing to do
+            value = None
+        return value
+
+    def draw(self, rng, data_dict):
+        order = [int(i) for i in rng.permutation(4)]
+        ranges = (self.brightness, self.contrast, self.saturation, self.hue)
+        factors = [None if r is None else float(rng.uniform(r[0], r[1])) for r in ranges]
+        for i in order:                                    # the per-step coin, in the order the steps run
+            if factors[i] is not None and not rng.random() < self.p:
+                factors[i] = None
+        return dict(order=order, **dict(zip(self.NAMES, factors)))
+
+    def fold(self, state, data_dict, params):
+        if "color" not in data_dict:
+            return
+        for i in params["order"]:
+            f = params[self.NAMES[int(i)]]
+            if f is None:
+                continue
+            if int(i) == 3 and not -0.5 <= f <= 0.5:
+                raise ValueError("hue_factor ({}) is not in [-0.5, 0.5].".format(f))
+            if int(i) != 3 and f < 0:
+                raise ValueError("{}_factor ({}) is not non-negative.".format(self.NAMES[int(i)], f))
+            state.add(data_dict, self.CODES[int(i)], f)
+
+
+@TRANSFORMS.register_module()
+class RandomColorSolarize(Transform):
+    """transform.py:178-194.  Registered, and it draws as the reference does (one rand() when `color` is there), but it leaves
+    `color` UNCHANGED: the reference computes the solarized colours into a local and returns data_dict without storing them,
+    so the shipped lists train on unsolarized views.  This class reproduces that; there is nothing to launch."""
+
+    def __init__(self, p=0.2, threshold=128):
+        self.p, self.threshold = p, threshold
+
+    def draw(self, rng, data_dict):
+        return dict(fired=bool(rng.random() < self.p)) if "color" in data_dict else dict(fired=False)
+
+    def apply(self, data_dict, params):
+        return data_dict
+
+
+# the per-point entries SphereCropRandomMaxPoints crops (transform.py:221-254): SphereCrop's and two more
+_CROP_MAX_POINTS_EXTRA = ("sh", "lang_feat_64")
+
+
+@TRANSFORMS.register_module()
+class SphereCropRandomMaxPoints(Transform):
+    """transform.py:197-255: point_max' = int(uniform(random_scale) * point_max); a sample with more points keeps the point_max'
+    nearest to a random point of it, in ascending-distance order (gpu_transforms.sphere_crop: ties by row index).
+    params["point_max"] / params["center_index"] replay a recorded call."""
+
+    def __init__(self, random_scale=(0.5, 1.0), point_max=80000):
+        self.random_scale, self.point_max = random_scale, point_max
+
+    def draw(self, rng, data_dict):
+        return dict(point_max=int(rng.uniform(self.random_scale[0], self.random_scale[1]) * self.point_max), u=float(rng.random()))
+
+    def apply(self, data_dict, params):
+        assert "coord" in data_dict
+        n = data_dict["coord"].shape[0]
+        ci = params.get("center_index")
+        if ci is None:
+            ci = min(int(params["u"] * n), n - 1)
+        return gt.sphere_crop(data_dict, int(params["point_max"]), None, "random", center_index=ci, extra_keys=_CROP_MAX_POINTS_EXTRA)
+
+
+@TRANSFORMS.register_module()
+class GSGaussianBlurVoxelOpc(Transform):
+    """transform.py:60-176: with probability p, the rows with opacity > 0.5 get `color` and the `extra_keys` among opacity / scale /
+    quat / normal replaced by the Gaussian-weighted mean (sigma ~ U(sigma[0], sigma[1]), truncate 2.0, scipy's `reflect` border)
+    over the masked voxels around them; with "quat" in extra_keys every row of quat is then normalised.  The reference fills a
+    DENSE grid over the view's bounding box for this; ss_voxel_blur hashes the occupied voxels and gathers (O(n) memory, no
+    readback).  Needs `grid_coord` (a GridSample with return_grid_coord in front) with UNIQUE rows -- one point per voxel, which
+    GridSample guarantees; with duplicates the reference keeps the last row written into a cell, the hash the first inserted.
+    Limits of the kernel: r = int(2 sigma + 0.5) <= 8, so the constructor refuses a sigma range that reaches 4.25; and a view
+    whose grid_coord spans 2^21 cells or more on an axis is left UNBLURRED (the normalisation of quat still runs) -- the kernel
+    says so in a device status word that apply() does not read, since reading it is a host sync.  GridSample refuses such an
+    extent itself, so a grid_coord that comes from it never gets there."""
+    KEYS = ("opacity", "scale", "quat", "normal")
+    MAX_RADIUS = 8
+
+    def __init__(self, p=0.5, sigma=(0.1, 2, 0), extra_keys=None):
+        if not 0 < sigma[0] <= sigma[1] or int(2.0 * sigma[1] + 0.5) > self.MAX_RADIUS:
+            raise ValueError(f"GSGaussianBlurVoxelOpc: sigma range {tuple(sigma[:2])} must be positive and stay below 4.25 "
+                             f"(the kernel gathers at most r = int(2 sigma + 0.5) = {self.MAX_RADIUS} cells)")
+        self.p, self.sigma = p, sigma
+        self.extra_keys = () if extra_keys is None else tuple(extra_keys)
+
+    def draw(self, rng, data_dict):
+        if not rng.random() < self.p:
+            return dict(fired=False, sigma=None)
+        return dict(fired=True, sigma=float(rng.uniform(self.sigma[0], self.sigma[1])))
+
+    def apply(self, data_dict, params):
+        if not params["fired"]:
+            return data_dict
+        if "grid_coord" not in data_dict:
+            raise AssertionError(f"grid_coord is required for GSGaussianBlur, but only {list(data_dict.keys())} is provided")
+        gc = data_dict["grid_coord"]
+        if not isinstance(gc, torch.Tensor) or not gc.is_cuda:
+            raise RuntimeError("GSGaussianBlurVoxelOpc: GPU tensors required (no CPU fallback)")
+        if gc.dtype != torch.int32 or not gc.is_contiguous():
+            gc = gc.to(torch.int32).contiguous()
+        opacity = _dev(data_dict["opacity"], "opacity")
+        mask = (opacity > 0.5).reshape(-1)
+        extra = {k: _dev(data_dict[k], k) for k in self.KEYS if k in self.extra_keys}
+        nv.voxel_blur_(gc, mask, _dev(data_dict["color"], "color", 3), params["sigma"], normalize_quat="quat" in extra, **extra)
+        return data_dict
+
+
+@TRANSFORMS.register_module()
+class ContrastiveViewsGenerator_SSL(Transform):
+    """transform.py:259-315: from clones of `view_keys`, two global views (global_base_transform, then global_transform0 /
+    global_transform1 on a clone each) and local_crop_num local views (local_base_transform, then local_transform on a clone
+    each) -> global_crop{0,1}_<key> and local_crop{i}_<key> for every key a view ends with; every other entry of data_dict stays.
+    The five sub-lists are Compose objects of this module (they fuse like their parent).  draw() hands over a seed; the generators
+    of the sub-list runs are spawned from it in the order global_base, local_base, global0, global1, local[0], local[1], ...;
+    params["views"] replays one recorded params list per run in that same order."""
+
+    def __init__(self, view_keys=("coord", "color", "normal", "origin_coord"), global_base_transform=None, local_base_transform=None,
+                 global_transform0=None, global_transform1=None, local_transform=None, local_crop_num=4):
+        self.view_keys = view_keys
+        self.global_base_transform = Compose(global_base_transform)
+        self.local_base_transform = Compose(local_base_transform)
+        self.global_transform0 = Compose(global_transform0)
+        self.global_transform1 = Compose(global_transform1)
+        self.local_transform = Compose(local_transform)
+        self.local_crop_num = local_crop_num
+
+    def set_fuse(self, fuse):
+        for c in (self.global_base_transform, self.local_base_transform, self.global_transform0, self.global_transform1,
+                  self.local_transform):
+            c.set_fuse(fuse)
+
+    def draw(self, rng, data_dict):
+        return dict(seed=_seed(rng))
+
+    def _clone(self, d):
+        return {k: (d[k].clone() if isinstance(d[k], torch.Tensor) else copy.deepcopy(d[k])) for k in self.view_keys}
+
+    def apply(self, data_dict, params):
+        runs = 4 + self.local_crop_num
+        views = params.get("views")
+        if views is not None and len(views) != runs:
+            raise ValueError(f"ContrastiveViewsGenerator_SSL: {runs} params lists expected, got {len(views)}")
+        rngs = [None] * runs if views is not None else \
+            [np.random.default_rng(s) for s in np.random.SeedSequence(int(params["seed"])).spawn(runs)]
+
+        def run(compose, d, k):
+            return compose(d, params=None if views is None else views[k], rng=rngs[k])
+        global_base = run(self.global_base_transform, self._clone(data_dict), 0)
+        global0 = run(self.global_transform0, self._clone(global_base), 2)
+        global1 = run(self.global_transform1, self._clone(global_base), 3)
+        local_base = run(self.local_base_transform, self._clone(data_dict), 1)
+        local = [run(self.local_transform, self._clone(local_base), 4 + i) for i in range(self.local_crop_num)]
+        for key, value in global0.items():
+            data_dict["global_crop0_" + key] = value
+        for key, value in global1.items():
+            data_dict["global_crop1_" + key] = value
+        for i, d in enumerate(local):
+            for key, value in d.items():
+                data_dict["local_crop{}_".format(i) + key] = value
+        return data_dict
+
+
+@TRANSFORMS.register_module()
+class CollectContrast(Transform):
+    """transform.py:20-56: every entry whose name starts with one of `keys_prefix`, one [n] offset tensor per entry of
+    offset_keys_dict (n = rows of the named entry) and every `<name>_keys=(...)` as `<name>`, the float32 column concatenation."""
+
+    def __init__(self, keys_prefix, offset_keys_dict=None, **kwargs):
+        self.keys = keys_prefix
+        self.offset_keys = dict(offset="coord") if offset_keys_dict is None else offset_keys_dict
+        self.kwargs = kwargs
+
+    def apply(self, data_dict, params):
+        data = dict()
+        for key in ([self.keys] if isinstance(self.keys, str) else self.keys):
+            for key_i in data_dict.keys():
+                if key_i.startswith(key):
+                    data[key_i] = data_dict[key_i]
+        for key, value in self.offset_keys.items():
+            data[key] = torch.tensor([data_dict[value].shape[0]], device=data_dict[value].device)
+        for name, keys in self.kwargs.items():
+            assert isinstance(keys, (list, tuple))
+            data[name.replace("_keys", "")] = torch.cat([data_dict[k].float() for k in keys], dim=1)
+        return data
+
+
 class Compose:
     """The reference's Compose (transform.py:1667-1677) with a seedable host Generator for every draw and, with fuse=True, runs of
     rigid ops and of colour ops folded into one kernel pass each (module docstring).  `params` replays one recorded dict per op."""
@@ -681,15 +942,24 @@ class Compose:
     def __init__(self, cfg=None, fuse=True, seed=None):
         self.cfg = cfg if cfg is not None else []
         self.transforms = [TRANSFORMS.build(c) if isinstance(c, dict) else c for c in self.cfg]
-        self.fuse = fuse
         self.rng = np.random.default_rng(seed)
+        self.set_fuse(fuse)
 
-    def __call__(self, data_dict, params=None):
+    def set_fuse(self, fuse):
+        """fuse / do not fuse, here and in the sub-lists of a nested ContrastiveViewsGenerator_SSL"""
+        self.fuse = fuse
+        for t in self.transforms:
+            if hasattr(t, "set_fuse"):
+                t.set_fuse(fuse)
+
+    def __call__(self, data_dict, params=None, rng=None):
+        """rng: the Generator of this call's draws (a nested list is handed one per run); default: the list's own."""
         if params is not None and len(params) != len(self.transforms):
             raise ValueError("Compose: one params dict per transform")
+        rng = self.rng if rng is None else rng
         state = None
         for i, t in enumerate(self.transforms):
-            p = params[i] if params is not None else t.draw(self.rng, data_dict)
+            p = params[i] if params is not None else t.draw(rng, data_dict)
             fam = t.family if self.fuse else None
             if state is not None and state.family != fam:
                 state.flush(data_dict)
