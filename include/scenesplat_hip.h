@@ -511,6 +511,41 @@ size_t ss_voxel_blur_workspace_bytes(int64_t n);
 int ss_voxel_blur(const int32_t* grid_coord, const uint8_t* mask, int64_t n, float* color, float* opacity, float* scale, float* quat,
                   float* normal, int normalize_quat, float sigma, void* workspace, size_t workspace_bytes, ss_stream_t stream);
 
+/* ---- SimDINO pretraining model (csrc/ssl_model.hip; pointcept/models/simdinov2.py:191-302, point_transformer_v3m1_ssl.py:733-737) ----
+ * Mask generator.  offset (num_batches) int32 = inclusive row ends of the samples, num_batches <= ss_mask_max_samples().
+ * ss_mask_keys: keys[i] = sample | z | y | x (ss_mask_key_bits() bits) of cell = floor(float(grid_coord) / mask_grid_size), IEEE divide;
+ *   sorting them orders a sample's cells as torch_cluster's grid index does (x fastest).  status[0] is set to 1 when a cell leaves
+ *   [0, 2^17) (the caller zeroes it and reads it with the patch counts).
+ * ss_mask_patches: cluster / n_out as ss_pool_partition wrote them over a stable argsort `order` of the keys -> patch_start
+ *   (num_batches + 1), patch_count (num_batches), patch_id (n) = rank of the row's cell among the occupied cells of its sample.
+ * ss_mask_select: mask[i] = selected[patch_start[b] + patch_id[i]] (patch_id NULL: selected[i], the `splats` mode); index = the masked
+ *   rows ascending, weight[j] = sample_weight[sample of index[j]] (fp16 bits), count[0] = how many; index / weight have capacity n,
+ *   block_counts ss_mask_select_blocks(n) int32.  Ordered three-pass compaction: no atomics. */
+int ss_mask_max_samples(void);
+int ss_mask_key_bits(void);
+int ss_mask_keys(const int32_t* grid_coord, const int32_t* offset, int num_batches, int64_t n, float mask_grid_size, int64_t* keys,
+                 int32_t* status, ss_stream_t stream);
+int ss_mask_patches(const int32_t* cluster, const int32_t* order, const int32_t* offset, int num_batches, int64_t n, const int32_t* n_out,
+                    int32_t* patch_start, int32_t* patch_count, int32_t* patch_id, ss_stream_t stream);
+int ss_mask_select_blocks(int64_t n);
+int ss_mask_select(const uint8_t* selected, const int32_t* patch_id, const int32_t* patch_start, const int32_t* offset, int num_batches,
+                   int64_t n, const uint16_t* sample_weight, uint8_t* mask, int32_t* index, uint16_t* weight, int32_t* count,
+                   int32_t* block_counts, ss_stream_t stream);
+/* Mask token.  x / out / g / dx (n, channels) f32 or bf16 (dtype), mask (n) bytes, token (channels) f32.
+ * fwd: out[i] = mask[i] ? token : x[i].  bwd: dx[i] = mask[i] ? 0 : g[i]; dtoken[c] = sum of the masked g[i][c] in fp32: workgroup w of
+ * ss_mask_token_bwd_blocks(n) owns ss_mask_token_bwd_span(n) consecutive rows, 256 / channels row slots add every (256 / channels)-th row
+ * in order, the slots are added in order, then the workgroups in order (partial: blocks x channels floats).  channels <= 256. */
+int ss_mask_token_fwd(const void* x, int dtype, const uint8_t* mask, const float* token, int64_t n, int channels, void* out,
+                      ss_stream_t stream);
+int ss_mask_token_bwd_blocks(int64_t n);
+int64_t ss_mask_token_bwd_span(int64_t n);
+int ss_mask_token_bwd(const void* g, int dtype, const uint8_t* mask, int64_t n, int channels, void* dx, float* partial, float* dtoken,
+                      ss_stream_t stream);
+/* Grouped EMA of the teacher: t = (m * t) + (alpha * s) for every pair in one launch, each product and the sum rounded to fp32
+ * (torch._foreach_mul_ + torch._foreach_add_(alpha=)).  desc 4 int64 per pair {t, s f32 pointers, numel, flags}; wg_start and flags
+ * as ss_adamw_group. */
+int ss_ema_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, float m, float alpha, ss_stream_t stream);
+
 /* ---- libs/pointops, pointops2, pointgroup_ops (fp32 features, int32 indices, offset batches) ------- */
 /* libs/pointops/src/knn_query/knn_query_cuda.cpp:7-16; nsample <= 128; idx -1 / dist2 1e10 padding */
 int ss_knn_query(int m, int nsample, const float* xyz, const float* new_xyz, const int32_t* offset,

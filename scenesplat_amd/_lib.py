@@ -142,6 +142,17 @@ PROTOTYPES = {
     "ss_voxel_blur_table_size": (c_i64, [c_i64]),
     "ss_voxel_blur_workspace_bytes": (c_sz, [c_i64]),
     "ss_voxel_blur": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_sz, c_p]),
+    "ss_mask_max_samples": (c_i, []),
+    "ss_mask_key_bits": (c_i, []),
+    "ss_mask_keys": (c_i, [c_p, c_p, c_i, c_i64, c_f, c_p, c_p, c_p]),
+    "ss_mask_patches": (c_i, [c_p, c_p, c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "ss_mask_select_blocks": (c_i, [c_i64]),
+    "ss_mask_select": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "ss_mask_token_fwd": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),
+    "ss_mask_token_bwd_blocks": (c_i, [c_i64]),
+    "ss_mask_token_bwd_span": (c_i64, [c_i64]),
+    "ss_mask_token_bwd": (c_i, [c_p, c_i, c_p, c_i64, c_i, c_p, c_p, c_p, c_p]),
+    "ss_ema_group": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
     "ss_knn_grid_table_size": (c_i64, [c_i64]),
     "ss_knn_grid_workspace_bytes": (c_sz, [c_i64]),
     "ss_knn_grid_keys": (c_i, [c_p, c_p, c_i, c_i64, c_f, c_f, c_f, c_f, c_p, c_p]),

@@ -1303,3 +1303,52 @@ def pdnorm_modulation(group, context):
         o.pdnorm_eff = True            # (read by _eff_stage)
     n = len(group.rows)
     return list(zip(outs[:n], outs[n:]))
+
+
+# ---- mask token of the SimDINO backbone (point_transformer_v3m1_ssl.py:733-737) ------------------------------------------------------
+class _MaskToken(torch.autograd.Function):
+    """out[i] = token where mask[i] else x[i] (a select: bit-exact); backward dx = g with the masked rows zeroed and dtoken = the column
+    sums of the masked rows of g, accumulated in fp32 in a fixed order (csrc/ssl_model.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, mask, token):
+        ctx.save_for_backward(mask)
+        ctx.token_meta = (token.shape, token.dtype)
+        return nv.mask_token_fwd(x.contiguous(), mask, token.detach().reshape(-1).float().contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        mask, = ctx.saved_tensors
+        shape, dtype = ctx.token_meta
+        dx, dtoken = nv.mask_token_bwd(g.contiguous(), mask)
+        return (dx if ctx.needs_input_grad[0] else None), None, (dtoken.reshape(shape).to(dtype) if ctx.needs_input_grad[2] else None)
+
+
+def mask_token(x, mask, token):
+    """x (n, C) fp32 / bf16 with the rows of `mask` (n, bool) replaced by `token` ((1, C) or (C,))."""
+    return _MaskToken.apply(x, mask, token)
+
+
+class _GatherRows(torch.autograd.Function):
+    """out[j] = src[index[j]] for unique ascending row indices (a compacted boolean mask); backward scatters into zeros."""
+
+    @staticmethod
+    def forward(ctx, src, index):
+        ctx.save_for_backward(index)
+        ctx.n_src = src.shape[0]
+        return nv.gather_rows(src.contiguous(), index)
+
+    @staticmethod
+    def backward(ctx, g):
+        index, = ctx.saved_tensors
+        dsrc = torch.zeros((ctx.n_src, g.shape[1]), dtype=g.dtype, device=g.device)
+        if index.numel():
+            nv.scatter_rows(g.contiguous(), index, dsrc)
+        return dsrc, None
+
+
+def gather_rows(src, index):
+    """src[index] for an int32 vector of unique rows, without the host sync of boolean indexing; differentiable in src."""
+    if index.numel() == 0:
+        return src[:0]
+    return _GatherRows.apply(src, index)

@@ -1526,3 +1526,119 @@ def pdnorm_mod_bwd(context, tab, ops, dgeff, dbeff, split_row=0):
     dg = [out[wtot + 2 * total + o[l]:wtot + 2 * total + o[l + 1]] if tab.affine[l][0] else None for l in range(n)]
     dbt = [out[wtot + 3 * total + o[l]:wtot + 3 * total + o[l + 1]] if tab.affine[l][1] else None for l in range(n)]
     return dcontext, dW, db, dg, dbt
+
+
+# ---- SimDINO pretraining model: patch masks, mask token, grouped EMA (csrc/ssl_model.hip) ------------------------------------------
+def _mask_offset(offset, n):
+    _req(offset, torch.int32, "offset")
+    B = offset.numel()
+    if B < 1 or B > lib().ss_mask_max_samples():
+        raise RuntimeError(f"mask generator: 1 .. {lib().ss_mask_max_samples()} samples per batch, got {B}")
+    return B
+
+
+def mask_patches(grid_coord, offset, mask_grid_size):
+    """Step 1 of the patch mask generator, on the device.  grid_coord (n,3) int32, offset (B) int32 (inclusive row ends).
+    -> patch_id (n) int32: rank of the row's mask cell floor(grid_coord / mask_grid_size) among the occupied cells of its sample (x
+    fastest, then y, then z); patch_start (B+1) int32; counts (B+1) int32 = the B patch counts followed by a status word that is non-zero
+    when a cell left the 17 bits per axis the sort key has (the caller reads counts on the host and must check it)."""
+    n = grid_coord.shape[0]
+    _req(grid_coord, torch.int32, "grid_coord", (n, 3))
+    B = _mask_offset(offset, n)
+    dev = grid_coord.device
+    counts = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    patch_start = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    patch_id = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return patch_id, patch_start, counts
+    keys = torch.empty((1, n), dtype=torch.int64, device=dev)
+    check(lib().ss_mask_keys(_p(grid_coord), _p(offset), B, n, float(mask_grid_size), _p(keys), _p(counts[B:]), _stream()), "ss_mask_keys")
+    order, _, _ = argsort_i64(keys, lib().ss_mask_key_bits(), want_inverse=False, want_sorted=False)
+    cluster, _, _, n_out = pool_partition(keys[0], order[0], 0)
+    check(lib().ss_mask_patches(_p(cluster), _p(order), _p(offset), B, n, _p(n_out), _p(patch_start), _p(counts), _p(patch_id), _stream()),
+          "ss_mask_patches")
+    return patch_id, patch_start, counts
+
+
+def mask_select(selected, patch_id, patch_start, offset, sample_weight, n):
+    """Step 2.  selected: one byte per patch (all samples, in patch_start order), or per row when patch_id is None (`splats`);
+    sample_weight (B) fp16.  -> mask (n) bool, index (n capacity) int32 ascending masked rows, weight (n capacity) fp16,
+    count (1) int32 on the device."""
+    _req(selected, torch.uint8, "selected"); _req(sample_weight, torch.float16, "sample_weight", (offset.numel(),))
+    B = _mask_offset(offset, n)
+    dev = offset.device
+    if patch_id is not None:
+        _req(patch_id, torch.int32, "patch_id", (n,)); _req(patch_start, torch.int32, "patch_start", (B + 1,))
+    elif selected.numel() != n:
+        raise RuntimeError("selected: one byte per row without patch ids")
+    mask = torch.empty(n, dtype=torch.bool, device=dev)
+    index = torch.empty(n, dtype=torch.int32, device=dev)
+    weight = torch.empty(n, dtype=torch.float16, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    blocks = torch.empty(lib().ss_mask_select_blocks(n), dtype=torch.int32, device=dev)
+    check(lib().ss_mask_select(_p(selected), _p(patch_id), _p(patch_start), _p(offset), B, n, _p(sample_weight), _p(mask), _p(index),
+                               _p(weight), _p(count), _p(blocks), _stream()), "ss_mask_select")
+    return mask, index, weight, count
+
+
+def _mask_rows(mask, n):
+    m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    return _req(m, torch.uint8, "mask", (n,))
+
+
+def mask_token_fwd(x, mask, token):
+    """out[i] = token where mask[i] else x[i].  x (n, C) fp32 / bf16, mask (n) bool, token (C) fp32."""
+    n, C = x.shape
+    _req(x, None, "x"); _req(token, torch.float32, "token")
+    if token.numel() != C:
+        raise RuntimeError("token: one value per channel")
+    out = torch.empty_like(x)
+    check(lib().ss_mask_token_fwd(_p(x), dtype_code(x), _p(_mask_rows(mask, n)), _p(token), n, C, _p(out), _stream()), "ss_mask_token_fwd")
+    return out
+
+
+def mask_token_bwd(g, mask):
+    """-> dx (n, C) = g with the masked rows zeroed, dtoken (C) fp32 = column sums of the masked rows (fixed order: reproducible)."""
+    n, C = g.shape
+    _req(g, None, "g")
+    if C > 256:
+        raise RuntimeError("mask token: at most 256 channels")
+    dx = torch.empty_like(g)
+    dtoken = torch.empty(C, dtype=torch.float32, device=g.device)
+    partial = torch.empty((lib().ss_mask_token_bwd_blocks(n), C), dtype=torch.float32, device=g.device)
+    check(lib().ss_mask_token_bwd(_p(g), dtype_code(g), _p(_mask_rows(mask, n)), n, C, _p(dx), _p(partial), _p(dtoken), _stream()),
+          "ss_mask_token_bwd")
+    return dx, dtoken
+
+
+def ema_group(teacher, student, m, cache=None):
+    """ONE launch: t = m * t + (1 - m) * s for every pair, in place.  alpha = 1 - m is formed in double and rounded to fp32 once, as
+    torch._foreach_add_(alpha=1 - m) does.  The caller bumps the version counters of `teacher` (the kernel writes through raw pointers).
+    cache: a dict the caller keeps between calls; while every tensor stays where it was (same data pointers) the checked and uploaded
+    descriptor table is reused, and a call is the pointer comparison plus the launch."""
+    import numpy as np
+    if len(teacher) != len(student):
+        raise RuntimeError("ema_group: one student tensor per teacher tensor")
+    if not len(teacher):
+        return
+    m = float(m)
+    key = tuple(t.data_ptr() for t in teacher) + tuple(s.data_ptr() for s in student)
+    if cache is not None and cache.get("key") == key:
+        d_dev, s_dev, n, total = cache["launch"]
+        check(lib().ss_ema_group(_p(d_dev), _p(s_dev), n, total, m, 1.0 - m, _stream()), "ss_ema_group")
+        return
+    dev = _req(teacher[0], torch.float32, "teacher[0]").device
+    for j, (t, s) in enumerate(zip(teacher, student)):
+        _optim_check(t, None, dev, f"teacher[{j}]"); _optim_check(s, t.numel(), dev, f"student[{j}]")
+    pairs = [(t, s) for t, s in zip(teacher, student) if t.numel()]
+    if not pairs:
+        return
+    starts = _optim_starts([t.numel() for t, _ in pairs])
+    desc = np.zeros((len(pairs), 4), dtype=np.int64)
+    desc[:, 0], desc[:, 1] = [t.data_ptr() for t, _ in pairs], [s.data_ptr() for _, s in pairs]
+    desc[:, 2] = [t.numel() for t, _ in pairs]
+    desc[:, 3] = ((desc[:, 0] | desc[:, 1]) & 15) == 0
+    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
+    if cache is not None and not torch.cuda.is_current_stream_capturing():
+        cache["key"], cache["launch"] = key, (d_dev, s_dev, len(pairs), starts[-1])
+    check(lib().ss_ema_group(_p(d_dev), _p(s_dev), len(pairs), starts[-1], m, 1.0 - m, _stream()), "ss_ema_group")

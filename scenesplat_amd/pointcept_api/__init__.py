@@ -1,6 +1,6 @@
 """Host-side mirror of the pointcept interfaces the hot path sits behind (registries,
 ``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, ``PDNorm`` / ``PPT-v1m2``, trainer/hook API, the training transforms, the open-vocabulary tester)."""
-from .registry import HOOKS, LOSSES, MODELS, MODULES, TESTERS, TRAINERS, TRANSFORMS, Registry, build_model  # noqa: F401
+from .registry import HOOKS, LOSSES, MODELS, MODULES, PRETRAINERS, TESTERS, TRAINERS, TRANSFORMS, Registry, build_model  # noqa: F401
 from .structure import Point  # noqa: F401
 from . import ptv3  # noqa: F401  (registers PT-v3m1)
 from . import lang  # noqa: F401  (registers LangPretrainer and the criteria)
@@ -17,3 +17,7 @@ from . import ppt  # noqa: F401  (registers PPT-v1m2)
 from .pdnorm import PDNorm  # noqa: F401  (registered in MODULES)
 from . import tester  # noqa: F401  (registers ZeroShotSemSegTester)
 from .tester import TesterBase, ZeroShotSemSegTester, final_metrics, gather_records, merge_records  # noqa: F401
+from . import ssl  # noqa: F401  (registers PT-v3m1-simdino and DefaultContrastiverSimDinoV2; engine registers DefaultSSLPreTrainer)
+from .ssl import (CosinePatchLoss, CosineScheduler, DefaultContrastiverSimDinoV2, DINOHead, MCRLoss,  # noqa: F401
+                  PointTransformerV3_SIMDINO)
+from .engine import DefaultSSLPreTrainer  # noqa: F401

@@ -20,7 +20,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from ..optim import FusedAdamW
-from .registry import HOOKS, MODELS, TRAINERS, Registry
+from .registry import HOOKS, MODELS, PRETRAINERS, TRAINERS, Registry
 
 OPTIMIZERS = Registry("optimizers")
 OPTIMIZERS.register_module(module=torch.optim.SGD, name="SGD")
@@ -489,3 +489,50 @@ class MultiDatasetTrainer(Trainer):
         cfg["scheduler"] = sched
         super().__init__(cfg, train_loader=train_loader, logger=logger, val_loader=val_loader)
         self.comm_info["iter_per_epoch"] = len(train_loader)
+
+
+# ---- self-supervised pretraining (engines/pretrain.py:114-230) -------------------------------------------------------------------------
+@PRETRAINERS.register_module("DefaultSSLPreTrainer")
+class DefaultSSLPreTrainer(Trainer):
+    """Trainer of the ssl-pretrain configs (model: DefaultContrastiverSimDinoV2).  A step is: teacher_temp = schedule.step(); forward,
+    backward; clip; optimizer and scheduler step; weight decay <- its schedule; update_teacher(momentum schedule.step()).  Schedules as
+    the reference builds them over the scheduler's total_steps: EMA momentum 0.9 -> 1, weight decay 0.04 -> 0.4, teacher temperature
+    0.04 -> 0.07 linearly over the first 60 % of the steps.  Eager only: the model reads patch counts on the host, so
+    cfg["steady_state"] is ignored (with a log line).  bf16 autocast, no GradScaler."""
+
+    def __init__(self, cfg, train_loader=None, logger=None, val_loader=None):
+        from .ssl import CosineScheduler
+        super().__init__(cfg, train_loader=train_loader, logger=logger, val_loader=val_loader)
+        total = int(self.scheduler.total_steps)
+        self.momentum_schedule = CosineScheduler(base_value=0.9, final_value=1, total_iters=total)
+        self.wd_schedule = CosineScheduler(base_value=0.04, final_value=0.4, total_iters=total)
+        self.teacher_temp_schedule = CosineScheduler(base_value=0.07, final_value=0.07, start_warmup_value=0.04,
+                                                     warmup_iters=int(0.6 * total), total_iters=int(0.6 * total))
+        self.last_momentum = None
+        if cfg.get("steady_state") and logger is not None:
+            logger("DefaultSSLPreTrainer: steady_state is ignored (the mask generator reads patch counts on the host: eager steps only)")
+
+    def run_step(self):
+        inp = self.comm_info["input_dict"]
+        teacher_temp = self.teacher_temp_schedule.step()
+        for k, v in inp.items():
+            if isinstance(v, torch.Tensor):
+                inp[k] = v.to(self.device, non_blocking=True)
+        amp = bool(self.cfg.get("enable_amp")) and self.device.type == "cuda"
+        with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=amp):
+            out = self.model(inp, teacher_temp)
+            loss = out["loss"]
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        if self.cfg.get("clip_grad") is not None and getattr(self.optimizer, "max_grad_norm", None) is None:
+            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.cfg["clip_grad"])
+        self.optimizer.step()
+        self.scheduler.step()
+        self.last_momentum = self.momentum_schedule.step()
+        wd = self.wd_schedule.step()
+        for group in self.optimizer.param_groups:
+            group["weight_decay"] = wd
+        model = getattr(self.model, "module", self.model)
+        if model.do_ema:
+            model.update_teacher(self.last_momentum)
+        self.comm_info["model_output_dict"] = out

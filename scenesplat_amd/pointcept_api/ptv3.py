@@ -459,13 +459,15 @@ class PointTransformerV3(PointModule):
             perms.append(torch.randperm(K).tolist() if down.shuffle_orders else list(range(K)))
         return perms
 
-    def plan_specs(self):
-        """Everything the float pipeline will ask the plan for: (window specs, conv kernel sizes)."""
+    def plan_specs(self, with_dec=True):
+        """Everything the float pipeline will ask the plan for: (window specs, conv kernel sizes).  with_dec=False: what an
+        encoder-only forward asks for (no decoder windows, conv widths of the encoder alone)."""
         K = len(self.order)
+        with_dec = with_dec and not self.cls_mode
         # which convs read the rulebook in WALK order is decided per level by the same predicates the forward uses
         # (ScenePlan.materialize -> conv_wants_walk below): the widths of the convs of each level travel with the spec
         wide = list(self.enc_channels)
-        if not self.cls_mode:
+        if with_dec:
             for s, c in enumerate(self.dec_channels_):
                 wide[s] = max(wide[s], c)
         walk = [[c for c in {self.enc_channels[s], wide[s]}] for s in range(self.num_stages)]
@@ -477,7 +479,7 @@ class PointTransformerV3(PointModule):
                 attn = getattr(enc, f"block{i}").attn
                 if not attn.enable_rpe:          # RPE windows follow the batch (rpe_window_size): built on first use
                     wins.append((s, i % K, attn.patch_size))
-        if not self.cls_mode:
+        if with_dec:
             for s in range(self.num_stages - 1):
                 dec = getattr(self.dec, f"dec{s}")
                 for i in range(self.dec_depths[s]):
@@ -486,7 +488,7 @@ class PointTransformerV3(PointModule):
                         wins.append((s, i % K, attn.patch_size))
         return wins, ks
 
-    def prepare_plan(self, data_dict, perms=None, stream=None):
+    def prepare_plan(self, data_dict, perms=None, stream=None, with_dec=True):
         """Build the integer plan of a batch ahead of time, optionally on a side stream so that its
         device->host round trips (depth, pooled sizes) never wait for the float pipeline of the
         previous step.  Pass the result as data_dict["plan"]."""
@@ -495,14 +497,14 @@ class PointTransformerV3(PointModule):
         perms = perms if perms is not None else self.draw_perms()
         if stream is None:
             plan = build_plan(data_dict["grid_coord"], data_dict["offset"], self.order, self.stride, perms)
-            plan.materialize(*self.plan_specs())
+            plan.materialize(*self.plan_specs(with_dec))
             return plan
         # NB: no wait on the main stream here -- that would park the plan behind the previous step's whole
         # backward.  The caller guarantees grid_coord / offset are already materialised (as a loader's
         # copy stream would after its own event).
         with torch.cuda.stream(stream):
             plan = build_plan(data_dict["grid_coord"], data_dict["offset"], self.order, self.stride, perms)
-            plan.materialize(*self.plan_specs())
+            plan.materialize(*self.plan_specs(with_dec))
             plan.ready_event = torch.cuda.Event()
             plan.ready_event.record(stream)
         return plan
@@ -596,14 +598,14 @@ class PointTransformerV3(PointModule):
             for m, (g, b) in zip(ms, SF.pdnorm_modulation(group, point["context"])):
                 m.__dict__["_resolved"] = ResolvedNorm(g, b, m.norm[idx])
 
-    def _draw_row_scales(self, levels, device):
+    def _draw_row_scales(self, levels, device, with_dec=True):
         """DropPath masks (one Bernoulli(keep)/keep scale per row and residual seam, timm DropPath on (n,C) rows as
         ptv3:333-336) of ALL blocks from one launch (plus the seed draw) per forward instead of 2 per seam (88)."""
         blocks = []
         for s in range(self.num_stages):
             enc = getattr(self.enc, f"enc{s}")
             blocks += [(getattr(enc, f"block{i}"), levels[s].n) for i in range(self.enc_depths[s])]
-        if not self.cls_mode:
+        if not self.cls_mode and with_dec:
             for s in reversed(range(self.num_stages - 1)):
                 dec = getattr(self.dec, f"dec{s}")
                 blocks += [(getattr(dec, f"block{i}"), levels[s].n) for i in range(self.dec_depths[s])]
@@ -628,7 +630,8 @@ class PointTransformerV3(PointModule):
             blk.__dict__["_row_scales"].append(scales[off:off + n])
             off += n
 
-    def forward(self, data_dict, perms=None):
+    def _begin_forward(self, data_dict, perms=None, with_dec=True):
+        """What every forward does before the float pipeline: -> (point, feat, plan)."""
         point = data_dict if isinstance(data_dict, Point) else Point(data_dict)
         feat = point["feat"]
         if not feat.is_cuda:
@@ -657,9 +660,12 @@ class PointTransformerV3(PointModule):
             torch.cuda.current_stream().wait_event(plan.ready_event)
             plan.record_stream(torch.cuda.current_stream())
             plan.ready_event = None
-        levels = plan.levels
         if self.training:
-            self._draw_row_scales(levels, feat.device)
+            self._draw_row_scales(plan.levels, feat.device, *(() if with_dec else (False,)))
+        return point, feat, plan
+
+    def forward(self, data_dict, perms=None):
+        point, feat, plan = self._begin_forward(data_dict, perms)
         if self._pdnorm():
             self._resolve_pdnorm(point)
             try:
@@ -670,8 +676,25 @@ class PointTransformerV3(PointModule):
         return self._forward_levels(point, feat, plan)
 
     def _forward_levels(self, point, feat, plan):
+        x, skips = self._forward_encoder(feat, plan)
+        lv = self.num_stages - 1
+        if not self.cls_mode:
+            x = self._forward_decoder(point, x, skips, plan)
+            lv = 0
+        out = Point(feat=x, plan=plan, level=lv)
+        for k in ("coord", "grid_coord", "offset"):
+            if lv == 0 and dict.__contains__(point, k):
+                out[k] = point[k]
+        return out
+
+    def _embedded(self, x, plan):
+        """Hook between the embedding and the first encoder stage (the SimDINO backbone puts its mask token here)."""
+        return x
+
+    def _forward_encoder(self, feat, plan):
+        """Embedding + encoder stages -> (features of the coarsest level, the skip features of levels 0 .. num_stages - 2)."""
         levels = plan.levels
-        x = self.embedding(feat, levels[0])
+        x = self._embedded(self.embedding(feat, levels[0]), plan)
         skips = []
         for s in range(self.num_stages):
             enc = getattr(self.enc, f"enc{s}")
@@ -684,29 +707,27 @@ class PointTransformerV3(PointModule):
                 wc = self._want_copy and conv_dtype_for(x.shape[1]) == torch.bfloat16
                 x, xb = getattr(enc, f"block{i}")(x, x if xb is None else xb, levels[s], wc and i + 1 < self.enc_depths[s])
             SF.stage_end()
-        lv = self.num_stages - 1
-        if not self.cls_mode:
-            # backward cut (data_dict["backward_cut"] = [], training): the inputs of the LAST decoder stage -- the first one the
-            # backward pass finishes, 52 % of the parameter bytes in the lang-pretrain model -- become leaves, so that the caller
-            # can run the backward in two calls (backward_in_two below) and start the gradient exchange of that stage in between
-            cut = point.get("backward_cut", None) if torch.is_grad_enabled() else None
-            for s in reversed(range(self.num_stages - 1)):
-                dec = getattr(self.dec, f"dec{s}")
-                if cut is not None and s == 0 and x.requires_grad:
-                    leaves = (x.detach().requires_grad_(True), skips[0].detach().requires_grad_(True))
-                    cut.extend([(x, leaves[0]), (skips[0], leaves[1])])
-                    x, skips[0] = leaves
-                SF.stage_begin(self._stage_linears(dec), levels[s].n)
-                x, conv_in = dec.up(x, skips[s], levels[s + 1])
-                xb = None
-                for i in range(self.dec_depths[s]):
-                    wc = self._want_copy and conv_dtype_for(x.shape[1]) == torch.bfloat16
-                    x, xb = getattr(dec, f"block{i}")(x, conv_in if i == 0 else (x if xb is None else xb), levels[s],
-                                                      wc and i + 1 < self.dec_depths[s])
-                SF.stage_end()
-            lv = 0
-        out = Point(feat=x, plan=plan, level=lv)
-        for k in ("coord", "grid_coord", "offset"):
-            if lv == 0 and dict.__contains__(point, k):
-                out[k] = point[k]
-        return out
+        return x, skips
+
+    def _forward_decoder(self, point, x, skips, plan):
+        """Decoder stages from the coarsest level's features down to level 0."""
+        levels = plan.levels
+        # backward cut (data_dict["backward_cut"] = [], training): the inputs of the LAST decoder stage -- the first one the
+        # backward pass finishes, 52 % of the parameter bytes in the lang-pretrain model -- become leaves, so that the caller
+        # can run the backward in two calls (backward_in_two below) and start the gradient exchange of that stage in between
+        cut = point.get("backward_cut", None) if torch.is_grad_enabled() else None
+        for s in reversed(range(self.num_stages - 1)):
+            dec = getattr(self.dec, f"dec{s}")
+            if cut is not None and s == 0 and x.requires_grad:
+                leaves = (x.detach().requires_grad_(True), skips[0].detach().requires_grad_(True))
+                cut.extend([(x, leaves[0]), (skips[0], leaves[1])])
+                x, skips[0] = leaves
+            SF.stage_begin(self._stage_linears(dec), levels[s].n)
+            x, conv_in = dec.up(x, skips[s], levels[s + 1])
+            xb = None
+            for i in range(self.dec_depths[s]):
+                wc = self._want_copy and conv_dtype_for(x.shape[1]) == torch.bfloat16
+                x, xb = getattr(dec, f"block{i}")(x, conv_in if i == 0 else (x if xb is None else xb), levels[s],
+                                                  wc and i + 1 < self.dec_depths[s])
+            SF.stage_end()
+        return x

@@ -78,6 +78,7 @@ MODULES = Registry("modules")
 LOSSES = Registry("losses")
 HOOKS = Registry("hooks")
 TRAINERS = Registry("trainers")
+PRETRAINERS = Registry("pretrainers")        # pointcept/engines/pretrain.py: the `train` entry of the ssl-pretrain configs
 TRANSFORMS = Registry("transforms")
 TESTERS = Registry("testers")
 
