@@ -89,20 +89,28 @@ int ss_window_attn_bwd(const void* qkv, const void* out, const void* dout, const
                        int64_t n_pad, int channels, int num_heads, float scale, int dtype, int impl, void* dqkv,
                        void* workspace, size_t workspace_bytes, ss_stream_t stream);
 
-/* ---- grouped fp32 -> bf16 cast of many tensors in one launch (the bf16 weight shadows; replaces one torch copy kernel per tensor).
- * desc: 3 int64 per tensor {src f32 pointer, dst bf16 pointer, numel}; wg_start (nprob + 1): first workgroup of each tensor at
- * 8192 elements per workgroup (ss_cast_bf16_group_elems_per_workgroup) */
+/* ---- grouped launches: many small problems in ONE launch --------------------------------------------------------------------
+ * Every entry point that takes (desc, wg_start, nprob, total_workgroups, ...) follows one contract.  desc: one row of int64 words
+ * per problem, (nprob, words) row-major; wg_start: nprob + 1 int32, wg_start[p] = first workgroup of problem p = the running total
+ * of the workgroup counts of the problems before it, wg_start[nprob] = total_workgroups < 2^31.  Both tables live in DEVICE memory.
+ * wg_start is non-decreasing and starts at 0; a problem may own no workgroup.  Workgroup b belongs to the LAST problem p with
+ * wg_start[p] <= b and works on that problem's piece b - wg_start[p].  nprob <= 0 or total_workgroups <= 0: SS_OK without a launch;
+ * a NULL table: SS_ERR_ARG (exceptions are stated at the entry).  Each entry below gives its descriptor words and what one workgroup
+ * owns (the unit that the workgroup count of a problem is rounded up in). */
+
+/* fp32 -> bf16 cast of many tensors (the bf16 weight shadows; replaces one torch copy kernel per tensor).
+ * desc: 3 words {src f32 pointer, dst bf16 pointer, numel}; a workgroup owns ss_cast_bf16_group_elems_per_workgroup() elements. */
 int ss_cast_bf16_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
 int ss_cast_bf16_group_elems_per_workgroup(void);
 
 /* ---- optimizer step: global gradient norm + AdamW update of all tensors of all parameter groups (replaces
  * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step, pointcept/engines/train.py:196-232).  Grouped launches as above:
- * wg_start (nprob + 1) at ss_optim_group_elems_per_workgroup() elements per workgroup; flags bit 0 = every pointer of the row is
- * 16-byte aligned (16-byte lanes; otherwise one element per lane).  No atomics: results are bitwise reproducible.
- * ss_grad_sqnorm_group: desc 3 int64 per tensor {g f32 pointer, numel, flags}; partials[w] = fp64 sum of squares of workgroup w.
+ * a workgroup owns ss_optim_group_elems_per_workgroup() elements; flags bit 0 = every pointer of the row is 16-byte aligned
+ * (16-byte lanes; otherwise one element per lane).  No atomics: results are bitwise reproducible.
+ * ss_grad_sqnorm_group: desc 3 words {g f32 pointer, numel, flags}; partials[w] = fp64 sum of squares of workgroup w.
  * ss_grad_norm_finish:  record[0] = total_norm = sqrt(sum of partials), record[1] = coef = min(1, max_norm / (total_norm + 1e-6)),
  *                       non-finite values propagating as in clip_grad_norm_(norm_type=2, error_if_nonfinite=False).
- * ss_adamw_group:       desc 10 int64 per tensor {p, g, m, v f32 pointers, numel, flags, then 8 fp32: 1 - lr*wd, 1 - beta1, beta2,
+ * ss_adamw_group:       desc 10 words {p, g, m, v f32 pointers, numel, flags, then 8 fp32: 1 - lr*wd, 1 - beta1, beta2,
  *                       1 - beta2, sqrt(1 - beta2^t), eps, lr / (1 - beta1^t), 0}; record as written by ss_grad_norm_finish (its
  *                       coef scales g on the fly) or NULL for coef = 1.  Writes p, m, v; g is only read. */
 int ss_optim_group_elems_per_workgroup(void);
@@ -117,9 +125,9 @@ int ss_adamw_group(const int64_t* desc, const int32_t* wg_start, int nprob, int 
  * silu(x) = x / (1 + exp(-x))) and [shift | scale] = W s + b per layer (W (2C, context_channels) row-major, b (2C)):
  *   gamma_eff = gamma * (1 + scale),  beta_eff = beta * (1 + scale) + shift,  ops = 1 + scale      (gamma = 1 / beta = 0 where NULL).
  * table: 14 int64 per layer {C, W, b, gamma | 0, beta | 0, gamma_eff, beta_eff, ops, dgamma_eff | 0, dbeta_eff | 0, dW, db,
- * dgamma | 0, dbeta | 0}, all fp32 pointers; the forward reads words 0-7, the backward words 0-1, 3-4 and 7-13.  wg_start
- * (num_layers + 1): first workgroup of each layer at ss_pdnorm_channels_per_workgroup() channels per workgroup.  vec4 != 0: 16-byte
- * accesses; the caller guarantees context_channels % 4 == 0 and 16-byte aligned context, W and dW.
+ * dgamma | 0, dbeta | 0}, all fp32 pointers; the forward reads words 0-7, the backward words 0-1, 3-4 and 7-13.  A grouped
+ * launch (above) with one problem per layer; a workgroup owns ss_pdnorm_channels_per_workgroup() channels.  Unlike the other grouped
+ * entries, num_layers < 0, and total_workgroups <= 0 with num_layers != 0, are SS_ERR_ARG.  vec4 != 0: 16-byte accesses; the caller guarantees context_channels % 4 == 0 and 16-byte aligned context, W and dW.
  * Backward: d_shift = dbeta_eff, d_scale = dgamma_eff * gamma + dbeta_eff * beta, db = [d_shift | d_scale], dW = db (x) s,
  * dgamma = dgamma_eff * ops, dbeta = dbeta_eff * ops, dcontext = silu'(context) * sum over layers of W^T db (a NULL dgamma_eff /
  * dbeta_eff counts as zeros).  partials: total_workgroups * context_channels floats of scratch; the sum over workgroups is finished
@@ -246,10 +254,10 @@ int ss_subm_conv_wgrad_pipe(const void* in, const void* dout, const int32_t* nbr
                             int taps, ss_stream_t stream);
 int ss_linear_wgrad(const void* x, const void* dy, float* dweight, float* dbias, int64_t m, int k_in, int n_out,
                     ss_stream_t stream);
-/* Grouped form: ONE launch for up to 128 independent nn.Linear weight gradients (the blocks of a pooled stage).
- * desc (nprob, 8) int64 in device memory, per problem {x, dy, dweight, dbias | 0, m, and three words filled by
- * ss_linear_wgrad_group_plan}; wg_start (nprob + 1) int32 device = running total of the workgroup counts that
- * ss_linear_wgrad_group_plan returns (host call, no launch; 0 = shape not eligible); every dweight / dbias zeroed. */
+/* Grouped launch (see "grouped launches") of up to 128 independent nn.Linear weight gradients (the blocks of a pooled stage);
+ * nprob > 128: SS_ERR_ARG.  desc: 8 words {x, dy, dweight, dbias | 0, m, and three words filled by ss_linear_wgrad_group_plan}; a
+ * problem owns the workgroup count that ss_linear_wgrad_group_plan returns (host call, no launch; 0 = shape not eligible); every
+ * dweight / dbias zeroed. */
 int ss_linear_wgrad_group_plan(int64_t m, int k_in, int n_out, int64_t* desc_words);
 /* ..._plan2: the same with launch_tiles = sum over the launch's problems of ss_linear_wgrad_tiles(k_in, n_out) (256 x 256 output
  * tiles): the K dimension of every problem is split so that the whole GROUP is one round of workgroups (one per CU). */
@@ -333,19 +341,20 @@ int ss_block_tail_bwd(const float* g_xout, const void* g_xcopy_bf16, const float
                       const void* u, const float* rs1, const float* rs2, const float* gamma, const void* wp_t, const void* w1_t,
                       const void* w2_t, float* g_mid, void* dfeat, void* dy2, void* du, void* dy1, float* part, int64_t n,
                       int channels, int nblocks, ss_stream_t stream);
-/* ONE launch reducing many partial-sum blocks (the dgamma / dbeta partials of a whole stage): desc (nprob, 4) int64 device =
- * {part (K, nb, C) f32, dst (K*C) f32, nb, C | (K*C) << 32}; wg_start (nprob + 1) int32 device, problem p owns
- * ceil(K*C / 256) workgroups; dst[k*C + c] = sum_b part[k][b][c]. */
-int ss_group_partial_sums_outputs_per_workgroup(void);   /* outputs (columns of K * C) one workgroup of ss_group_partial_sums owns */
+/* Grouped launch reducing many partial-sum blocks (the dgamma / dbeta partials of a whole stage): desc 4 words {part (K, nb, C) f32,
+ * dst (K*C) f32, nb, C | (K*C) << 32}; a workgroup owns ss_group_partial_sums_outputs_per_workgroup() of the K*C outputs;
+ * dst[k*C + c] = sum_b part[k][b][c]. */
+int ss_group_partial_sums_outputs_per_workgroup(void);
 int ss_group_partial_sums(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
-/* ss_transpose16_group: dst (cols, rows) = src (rows, cols)^T of 2-byte elements for many matrices in one launch (transposed bf16 copies of
- * nn.Linear weights: hipBLASLt's NT form of the dgrad GEMM dx = dy @ W, reference call site torch.nn.functional.linear backward under
- * point_transformer_v3m1_base.py:225-248).  desc (nprob, 4) int64 device = {src, dst, rows, cols}; wg_start (nprob + 1) int32 device =
- * running total of ceil(rows / 64) * ceil(cols / 64). */
+/* ss_transpose16_group: dst (cols, rows) = src (rows, cols)^T of 2-byte elements for many matrices in one grouped launch (transposed bf16
+ * copies of nn.Linear weights: hipBLASLt's NT form of the dgrad GEMM dx = dy @ W, reference call site torch.nn.functional.linear backward
+ * under point_transformer_v3m1_base.py:225-248).  desc 4 words {src, dst, rows, cols}; a workgroup owns one 64 x 64 tile (row-major over
+ * ceil(rows / 64) x ceil(cols / 64)). */
 int ss_transpose16_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
-/* ss_subm_weight_mirror_group: ss_subm_weight_mirror for many conv weights in one launch; desc (nprob, 5) int64 device = {w, wt, cout, taps,
- * cin}, wg_start = running total of taps * ceil(cout / 32) * ceil(cin / 32). */
-int ss_subm_weight_mirror_group_tile(void);   /* edge of the (cout x cin) tile one workgroup of ss_subm_weight_mirror_group owns */
+/* ss_subm_weight_mirror_group: ss_subm_weight_mirror for many conv weights in one grouped launch; desc 5 words {w, wt, cout, taps, cin};
+ * a workgroup owns one (tap, T x T) tile of (cout x cin) with T = ss_subm_weight_mirror_group_tile(): taps * ceil(cout / T) *
+ * ceil(cin / T) workgroups per problem. */
+int ss_subm_weight_mirror_group_tile(void);
 int ss_subm_weight_mirror_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
 /* g_v = g_xout + g_xcopy + LN'(g_h); g_x = g_v; g_y = rowscale*g_v; dgamma/dbeta partials (nblocks, C) */
 int ss_add_layernorm_bwd(const void* g_xout, int g_xout_dtype, const void* g_xcopy, int g_xcopy_dtype, const void* g_h,
@@ -542,7 +551,7 @@ int64_t ss_mask_token_bwd_span(int64_t n);
 int ss_mask_token_bwd(const void* g, int dtype, const uint8_t* mask, int64_t n, int channels, void* dx, float* partial, float* dtoken,
                       ss_stream_t stream);
 /* Grouped EMA of the teacher: t = (m * t) + (alpha * s) for every pair in one launch, each product and the sum rounded to fp32
- * (torch._foreach_mul_ + torch._foreach_add_(alpha=)).  desc 4 int64 per pair {t, s f32 pointers, numel, flags}; wg_start and flags
+ * (torch._foreach_mul_ + torch._foreach_add_(alpha=)).  desc 4 words {t, s f32 pointers, numel, flags}; workgroup size and flags
  * as ss_adamw_group. */
 int ss_ema_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, float m, float alpha, ss_stream_t stream);
 

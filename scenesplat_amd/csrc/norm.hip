@@ -8,7 +8,7 @@
 // partial sums (reduced by the caller), fp32 statistics throughout.
 // One wave per row, 4 elements per lane per step (16-byte fp32 / 8-byte bf16 accesses, fully
 // coalesced 1 KiB / 512 B per wave instruction); the row lives in registers between the two passes.
-#include "common.h"
+#include "grouped.h"
 #include "rowmath.h"
 #include "../../include/scenesplat_hip.h"
 
@@ -650,7 +650,7 @@ extern "C" int ss_bn_act_bwd_apply(const void* dy, int dy_dtype, const void* x, 
 // The backward seams above leave per-block partial sums of the affine gradients, part (K, nb, C) f32 (K = 2 or 4 parameter
 // vectors).  Reducing each with its own launch is 44 tiny kernels per step on the pooled levels; the stage identity node
 // (functional._StageParams) queues them and this kernel reduces ALL of a stage's partials in one launch.
-// desc: 4 int64 words per problem = {part, dst (K*C f32), nb, C | (K*C) << 32}; wg_start (nprob + 1): first workgroup.
+// desc: 4 int64 words per problem = {part, dst (K*C f32), nb, C | (K*C) << 32}.
 // A workgroup owns GPS_COLS consecutive outputs and splits the nb partial rows over 8 row groups (one thread per (output, group), LDS
 // reduce): the first form gave each output ONE thread that walked all nb <= 1024 rows -- a 256-step dependent chain on 60 workgroups,
 // 65 us per stage and 0.45 ms per step for a few MB of reads.
@@ -659,8 +659,7 @@ __global__ void __launch_bounds__(256)
 k_group_partial_sums(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob) {
   __shared__ float red[8][GPS_COLS];
   const int b = blockIdx.x;
-  int p = 0;
-  while (p + 1 < nprob && wg_start[p + 1] <= b) ++p;
+  const int p = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)p * 4;
   const float* part = reinterpret_cast<const float*>(d[0]);
   float* dst = reinterpret_cast<float*>(d[1]);
@@ -691,8 +690,7 @@ k_group_partial_sums(const int64_t* __restrict__ desc, const int32_t* __restrict
 extern "C" int ss_group_partial_sums_outputs_per_workgroup(void) { return GPS_COLS; }
 extern "C" int ss_group_partial_sums(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups,
                                      ss_stream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
   SS_LAUNCH(k_group_partial_sums, dim3((unsigned)total_workgroups), dim3(256), 0, stream, desc, wg_start, nprob);
   return SS_OK;
 }

@@ -4,30 +4,13 @@
 // build a parameter-sized temporary for the denominator.  Here the gradient is read once for the norm, then p, g, m, v are read
 // and p, m, v written once: 32 bytes per parameter for the update.  The clip coefficient never leaves the device.
 //
-// Grouped form of k_cast_bf16_group (rows.hip): a descriptor table with one row per tensor, wg_start (nprob + 1) with the first
-// workgroup of each tensor, a binary search for the owning tensor; a workgroup of 256 threads owns OPTG_PER_WG consecutive
-// elements of one tensor.  No atomics anywhere: every sum has a fixed order, so results are bitwise reproducible.
-#include "common.h"
+// Grouped launches (grouped.h), one descriptor row per tensor; a workgroup of 256 threads owns OPTG_PER_WG consecutive elements of
+// one tensor.  No atomics anywhere: every sum has a fixed order, so results are bitwise reproducible.
+#include "grouped.h"
 #include "../../include/scenesplat_hip.h"
 
 #define OPTG_PER_WG 8192
 #define OPTG_FLAG_VEC16 1        // every base pointer of the row is 16-byte aligned: 16-byte lanes; else one element per lane
-
-// tensor pointers come out of the descriptor table as integers: typed as global-address-space pointers they compile to global_load /
-// global_store (a plain float* from an integer is a generic pointer: flat_ instructions, which also occupy the LDS counter)
-typedef __attribute__((address_space(1))) float gf32;
-typedef __attribute__((address_space(1))) const float cgf32;
-typedef __attribute__((address_space(1))) f32x4_t gf32x4;
-typedef __attribute__((address_space(1))) const f32x4_t cgf32x4;
-__device__ __forceinline__ f32x4_t ld4(cgf32* p) { return *reinterpret_cast<cgf32x4*>(p); }
-__device__ __forceinline__ f32x4_t ld4(gf32* p) { return *reinterpret_cast<cgf32x4*>(p); }
-__device__ __forceinline__ void st4(gf32* p, f32x4_t v) { *reinterpret_cast<gf32x4*>(p) = v; }
-
-__device__ __forceinline__ int optg_owner(const int32_t* __restrict__ wg_start, int nprob, int b) {
-  int lo = 0, hi = nprob - 1;                         // last problem whose first workgroup is <= b
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (wg_start[mid] <= b) lo = mid; else hi = mid - 1; }
-  return lo;
-}
 
 // sum over the workgroup in a fixed order: lanes by xor-butterfly (every lane ends with the same value), then the 4 waves in order
 __device__ __forceinline__ double optg_block_sum(double x, double* lds) {
@@ -45,32 +28,19 @@ __global__ void __launch_bounds__(256)
 k_grad_sqnorm_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob, double* __restrict__ partials) {
   __shared__ double lds[4];
   const int b = blockIdx.x;
-  const int lo = optg_owner(wg_start, nprob, b);
+  const int lo = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)lo * 3;
   cgf32* g = reinterpret_cast<cgf32*>(d[0]);
-  const int64_t numel = d[1];
-  const int64_t e0 = (int64_t)(b - wg_start[lo]) * OPTG_PER_WG;
   double acc = 0.0;
-  if (d[2] & OPTG_FLAG_VEC16) {
-#pragma unroll
-    for (int i = 0; i < OPTG_PER_WG / (256 * 8); ++i) {
-      const int64_t e = e0 + ((int64_t)i * 256 + threadIdx.x) * 8;
-      if (e + 8 <= numel) {
+  group_span<OPTG_PER_WG, 8>(
+      (int64_t)(b - wg_start[lo]) * OPTG_PER_WG, d[1], d[2] & OPTG_FLAG_VEC16,
+      [&](int64_t e) {
         const f32x4_t a = ld4(g + e), c = ld4(g + e + 4);
         const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc += (double)x[k] * (double)x[k];
-      } else {
-        for (int64_t k = e; k < numel; ++k) acc += (double)g[k] * (double)g[k];
-      }
-    }
-  } else {
-#pragma unroll 4
-    for (int i = 0; i < OPTG_PER_WG / 256; ++i) {
-      const int64_t k = e0 + (int64_t)i * 256 + threadIdx.x;
-      if (k < numel) acc += (double)g[k] * (double)g[k];
-    }
-  }
+      },
+      [&](int64_t k) { acc += (double)g[k] * (double)g[k]; });
   const double s = optg_block_sum(acc, lds);
   if (threadIdx.x == 0) partials[b] = s;
 }
@@ -121,24 +91,20 @@ __device__ __forceinline__ void adamw_vec4(f32x4_t& p, const f32x4_t g, f32x4_t&
 __global__ void __launch_bounds__(256)
 k_adamw_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob, const float* __restrict__ record) {
   const int b = blockIdx.x;
-  const int lo = optg_owner(wg_start, nprob, b);
+  const int lo = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)lo * OPTG_ADAMW_WORDS;
   gf32* p = reinterpret_cast<gf32*>(d[0]);
   cgf32* g = reinterpret_cast<cgf32*>(d[1]);
   gf32* m = reinterpret_cast<gf32*>(d[2]);
   gf32* v = reinterpret_cast<gf32*>(d[3]);
-  const int64_t numel = d[4];
   float f[8];
   __builtin_memcpy(f, d + 6, sizeof(f));              // the row's last four words hold 8 floats
   AdamwScalars s;
   s.decay = f[0]; s.omb1 = f[1]; s.beta2 = f[2]; s.omb2 = f[3]; s.bc2_sqrt = f[4]; s.eps = f[5]; s.step_size = f[6];
   s.coef = record ? record[1] : 1.0f;
-  const int64_t e0 = (int64_t)(b - wg_start[lo]) * OPTG_PER_WG;
-  if (d[5] & OPTG_FLAG_VEC16) {
-#pragma unroll
-    for (int i = 0; i < OPTG_PER_WG / (256 * 8); ++i) {
-      const int64_t e = e0 + ((int64_t)i * 256 + threadIdx.x) * 8;
-      if (e + 8 <= numel) {
+  group_span<OPTG_PER_WG, 8>(
+      (int64_t)(b - wg_start[lo]) * OPTG_PER_WG, d[4], d[5] & OPTG_FLAG_VEC16,
+      [&](int64_t e) {
         f32x4_t pa = ld4(p + e), pb = ld4(p + e + 4);
         const f32x4_t ga = ld4(g + e), gb = ld4(g + e + 4);
         f32x4_t ma = ld4(m + e), mb = ld4(m + e + 4);
@@ -147,33 +113,20 @@ k_adamw_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_s
         st4(p + e, pa); st4(p + e + 4, pb);
         st4(m + e, ma); st4(m + e + 4, mb);
         st4(v + e, va); st4(v + e + 4, vb);
-      } else {
-        for (int64_t k = e; k < numel; ++k) {
-          float pk = p[k], mk = m[k], vk = v[k];
-          adamw_elem(pk, g[k], mk, vk, s);
-          p[k] = pk; m[k] = mk; v[k] = vk;
-        }
-      }
-    }
-  } else {
-#pragma unroll 4
-    for (int i = 0; i < OPTG_PER_WG / 256; ++i) {
-      const int64_t k = e0 + (int64_t)i * 256 + threadIdx.x;
-      if (k < numel) {
+      },
+      [&](int64_t k) {
         float pk = p[k], mk = m[k], vk = v[k];
         adamw_elem(pk, g[k], mk, vk, s);
         p[k] = pk; m[k] = mk; v[k] = vk;
-      }
-    }
-  }
+      });
 }
 
 extern "C" int ss_optim_group_elems_per_workgroup(void) { return OPTG_PER_WG; }
 
 extern "C" int ss_grad_sqnorm_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, double* partials,
                                     hipStream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start || !partials) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
+  if (!partials) return SS_ERR_ARG;
   SS_LAUNCH(k_grad_sqnorm_group, dim3((unsigned)total_workgroups), dim3(256), 0, stream, desc, wg_start, nprob, partials);
   return SS_OK;
 }
@@ -186,8 +139,7 @@ extern "C" int ss_grad_norm_finish(const double* partials, int num_partials, flo
 
 extern "C" int ss_adamw_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, const float* record,
                               hipStream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
   SS_LAUNCH(k_adamw_group, dim3((unsigned)total_workgroups), dim3(256), 0, stream, desc, wg_start, nprob, record);
   return SS_OK;
 }

@@ -5,24 +5,15 @@
 //   gamma_eff = gamma * (1 + scale),   beta_eff = beta * (1 + scale) + shift        (gamma = 1, beta = 0 for an affine-free norm)
 // and the fused norm kernels (norm.hip) run unchanged on gamma_eff / beta_eff.  What is left per layer is a (2C x Cc) matrix-vector
 // product: 64 of them in the lang-pretrain backbone (18,720 channels), a few microseconds of launch each as separate ops.  Here: a descriptor table with one
-// row per layer (the grouped form of optim.hip), 16 channels per workgroup, 4 per wave; the lanes of a wave stride over Cc and the
+// row per layer (a grouped launch, grouped.h), 16 channels per workgroup, 4 per wave; the lanes of a wave stride over Cc and the
 // two rows of W that a channel needs (c: shift, C + c: scale) are read once, coalesced.  Sums have a fixed order (lane-strided,
 // xor butterfly, waves in order, workgroup partials in order): no atomics, results are bitwise reproducible.
-#include "common.h"
+#include "grouped.h"
 #include "../../include/scenesplat_hip.h"
 
 #define PDN_WORDS 14          // int64 words per table row, see scenesplat_hip.h
 #define PDN_CH_PER_WG 16
 #define PDN_CH_PER_WAVE 4
-
-typedef __attribute__((address_space(1))) float gf32;
-typedef __attribute__((address_space(1))) const float cgf32;
-
-__device__ __forceinline__ int pdn_owner(const int32_t* __restrict__ wg_start, int nprob, int b) {
-  int lo = 0, hi = nprob - 1;                         // last layer whose first workgroup is <= b
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (wg_start[mid] <= b) lo = mid; else hi = mid - 1; }
-  return lo;
-}
 
 __device__ __forceinline__ float pdn_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float pdn_silu(float x) { return x / (1.0f + expf(-x)); }
@@ -38,15 +29,15 @@ template <int V> __device__ __forceinline__ PdnVec<V> pdn_ld(const float* p) {
 template <int V> __device__ __forceinline__ PdnVec<V> pdn_ld(cgf32* p) {
   PdnVec<V> r;
   if constexpr (V == 4) {
-    const f32x4_t t = *reinterpret_cast<__attribute__((address_space(1))) const f32x4_t*>(p);
+    const f32x4_t t = ld4(p);
     r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
   } else r.v[0] = *p;
   return r;
 }
 template <int V> __device__ __forceinline__ void pdn_st(gf32* p, const PdnVec<V>& r) {
   if constexpr (V == 4) {
-    f32x4_t t = {r.v[0], r.v[1], r.v[2], r.v[3]};
-    *reinterpret_cast<__attribute__((address_space(1))) f32x4_t*>(p) = t;
+    const f32x4_t t = {r.v[0], r.v[1], r.v[2], r.v[3]};
+    st4(p, t);
   } else *p = r.v[0];
 }
 
@@ -56,7 +47,7 @@ __global__ void __launch_bounds__(256)
 k_pdnorm_mod_fwd(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob, const float* __restrict__ context,
                  int Cc) {
   const int b = blockIdx.x;
-  const int lo = pdn_owner(wg_start, nprob, b);
+  const int lo = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)lo * PDN_WORDS;
   const int C = (int)d[0];
   cgf32* W = reinterpret_cast<cgf32*>(d[1]);
@@ -109,7 +100,7 @@ k_pdnorm_mod_bwd(const int64_t* __restrict__ desc, const int32_t* __restrict__ w
                  int Cc, float* __restrict__ partials) {
   __shared__ float lds[4][64 * V];
   const int b = blockIdx.x;
-  const int lo = pdn_owner(wg_start, nprob, b);
+  const int lo = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)lo * PDN_WORDS;
   const int C = (int)d[0];
   cgf32* W = reinterpret_cast<cgf32*>(d[1]);

@@ -3,7 +3,7 @@
 // Replaces, on the PTv3 path, feat[indices] / feat[inverse] indexing (ptv3:188,216,417,478) and
 // torch_scatter.segment_csr (ptv3:416-421).  Every source row and index is read once and every
 // destination row written once, 16 bytes per lane where the row width allows.
-#include "common.h"
+#include "grouped.h"
 #include "../../include/scenesplat_hip.h"
 
 template <typename V>
@@ -382,13 +382,12 @@ extern "C" int ss_gather_add_rows(const void* a, const void* b, const int32_t* i
 // The dgrad GEMM of nn.Linear, dx = dy @ W, runs 12-17 % faster on hipBLASLt when W arrives as a transposed contiguous copy (its NT
 // form; NN 0.41 / 0.45 / 0.50 ms vs NT 0.36 / 0.37 / 0.42 ms at the dec0 shapes, bit-identical results).  The copies are refreshed
 // together with the bf16 parameter shadows, all matrices of a model in this one launch.
-// desc: 4 int64 words per problem = {src, dst, rows, cols}; wg_start (nprob + 1): first workgroup; a workgroup owns one 64 x 64 tile.
+// desc: 4 int64 words per problem = {src, dst, rows, cols}; a workgroup owns one 64 x 64 tile.
 __global__ void __launch_bounds__(256)
 k_transpose16_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob) {
   __shared__ unsigned short tile[64][66];
   const int b = blockIdx.x;
-  int p = 0;
-  while (p + 1 < nprob && wg_start[p + 1] <= b) ++p;
+  const int p = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)p * 4;
   const unsigned short* src = reinterpret_cast<const unsigned short*>(d[0]);
   unsigned short* dst = reinterpret_cast<unsigned short*>(d[1]);
@@ -410,8 +409,7 @@ k_transpose16_group(const int64_t* __restrict__ desc, const int32_t* __restrict_
 }
 
 extern "C" int ss_transpose16_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, hipStream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
   SS_LAUNCH(k_transpose16_group, dim3((unsigned)total_workgroups), dim3(256), 0, stream, desc, wg_start, nprob);
   return SS_OK;
 }
@@ -419,36 +417,29 @@ extern "C" int ss_transpose16_group(const int64_t* desc, const int32_t* wg_start
 // ---- grouped fp32 -> bf16 cast: the bf16 shadows of ALL GEMM / conv weights of a model in ONE launch (round 3) ----------------
 // torch._foreach_copy_ with a dtype change falls back to one copy kernel per tensor: 206 launches and 1.2 ms per step for the
 // lang-pretrain model (profiles/r03_kernel_stats.md, first take).  desc: 3 int64 words per tensor = {src f32, dst bf16, numel};
-// wg_start (nprob + 1); a workgroup owns 8,192 consecutive elements of one tensor (tensor bases are allocator-aligned).
+// a workgroup owns 8,192 consecutive elements of one tensor (tensor bases are allocator-aligned).
 #define CASTG_PER_WG 8192
 __global__ void __launch_bounds__(256)
 k_cast_bf16_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob) {
   const int b = blockIdx.x;
-  int lo = 0, hi = nprob - 1;                       // last problem whose first workgroup is <= b
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (wg_start[mid] <= b) lo = mid; else hi = mid - 1; }
+  const int lo = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)lo * 3;
   const float* src = reinterpret_cast<const float*>(d[0]);
   unsigned short* dst = reinterpret_cast<unsigned short*>(d[1]);
-  const int64_t numel = d[2];
-  const int64_t e0 = (int64_t)(b - wg_start[lo]) * CASTG_PER_WG;
-#pragma unroll
-  for (int i = 0; i < CASTG_PER_WG / (256 * 8); ++i) {
-    const int64_t e = e0 + ((int64_t)i * 256 + threadIdx.x) * 8;
-    if (e + 8 <= numel) {
-      const float4 a = *reinterpret_cast<const float4*>(src + e), c = *reinterpret_cast<const float4*>(src + e + 4);
-      uint4 o;
-      o.x = pack_bf16x2(a.x, a.y); o.y = pack_bf16x2(a.z, a.w); o.z = pack_bf16x2(c.x, c.y); o.w = pack_bf16x2(c.z, c.w);
-      *reinterpret_cast<uint4*>(dst + e) = o;
-    } else {
-      for (int64_t k = e; k < numel; ++k) dst[k] = f32_to_bf16(src[k]);
-    }
-  }
+  group_span<CASTG_PER_WG, 8>(                      // no flag word: always the 16-byte path
+      (int64_t)(b - wg_start[lo]) * CASTG_PER_WG, d[2], true,
+      [&](int64_t e) {
+        const float4 a = *reinterpret_cast<const float4*>(src + e), c = *reinterpret_cast<const float4*>(src + e + 4);
+        uint4 o;
+        o.x = pack_bf16x2(a.x, a.y); o.y = pack_bf16x2(a.z, a.w); o.z = pack_bf16x2(c.x, c.y); o.w = pack_bf16x2(c.z, c.w);
+        *reinterpret_cast<uint4*>(dst + e) = o;
+      },
+      [&](int64_t k) { dst[k] = f32_to_bf16(src[k]); });
 }
 
 extern "C" int ss_cast_bf16_group_elems_per_workgroup(void) { return CASTG_PER_WG; }
 extern "C" int ss_cast_bf16_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, hipStream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
   SS_LAUNCH(k_cast_bf16_group, dim3((unsigned)total_workgroups), dim3(256), 0, stream, desc, wg_start, nprob);
   return SS_OK;
 }
@@ -485,14 +476,13 @@ extern "C" int ss_row_keep_scales(const int64_t* seed, const float* keep, float*
 }
 
 // ---- grouped form of k_subm_weight_mirror: the dgrad weights of ALL convs of a model in one launch (refreshed with the bf16 shadows) ----
-// desc: 5 int64 words per problem = {w, wt, cout, taps, cin}; wg_start (nprob + 1); a workgroup owns one (tap, WMG_TILE x WMG_TILE) tile.
+// desc: 5 int64 words per problem = {w, wt, cout, taps, cin}; a workgroup owns one (tap, WMG_TILE x WMG_TILE) tile.
 #define WMG_TILE 64      // 64 x 64 elements: 128-byte rows on both the read and the write side (32 x 32 moved 64-byte half lines: 142 us per refresh)
 __global__ void __launch_bounds__(256)
 k_subm_weight_mirror_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob) {
   __shared__ unsigned short tile[WMG_TILE][WMG_TILE + 2];
   const int b = blockIdx.x;
-  int p = 0;
-  while (p + 1 < nprob && wg_start[p + 1] <= b) ++p;
+  const int p = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)p * 5;
   const unsigned short* w = reinterpret_cast<const unsigned short*>(d[0]);
   unsigned short* wt = reinterpret_cast<unsigned short*>(d[1]);
@@ -518,8 +508,7 @@ k_subm_weight_mirror_group(const int64_t* __restrict__ desc, const int32_t* __re
 extern "C" int ss_subm_weight_mirror_group_tile(void) { return WMG_TILE; }
 extern "C" int ss_subm_weight_mirror_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups,
                                            hipStream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
   SS_LAUNCH(k_subm_weight_mirror_group, dim3((unsigned)total_workgroups), dim3(256), 0, stream, desc, wg_start, nprob);
   return SS_OK;
 }

@@ -7,7 +7,7 @@
 //                    per-row fp16 weights, compacted by a three-pass ordered scan.
 //   mask token       out = mask ? token : x, and its backward (dx, dtoken).
 //   grouped EMA      teacher = m * teacher + (1 - m) * student over a descriptor table, the layout of ss_adamw_group (csrc/optim.hip).
-#include "common.h"
+#include "grouped.h"
 #include "../../include/scenesplat_hip.h"
 
 namespace {
@@ -219,14 +219,10 @@ k_mask_token_finish(const float* __restrict__ partial, int nb, int C, float* __r
 }
 
 // ---- grouped EMA ---------------------------------------------------------------------------------------------------------------------------
-// desc: 4 int64 words per pair = {teacher f32 pointer, student f32 pointer, numel, flags}; the grouping of ss_adamw_group.  The arithmetic
+// desc: 4 int64 words per pair = {teacher f32 pointer, student f32 pointer, numel, flags}; flags as in optim.hip.  The arithmetic
 // is torch._foreach_mul_(t, m) followed by torch._foreach_add_(t, s, alpha = 1 - m) with every rounding kept: (m * t) + (alpha * s), three
 // fp32 roundings, never contracted into an fma.
 #define EMA_PER_WG 8192
-typedef __attribute__((address_space(1))) float gf32;
-typedef __attribute__((address_space(1))) const float cgf32;
-typedef __attribute__((address_space(1))) f32x4_t gf32x4;
-typedef __attribute__((address_space(1))) const f32x4_t cgf32x4;
 
 __device__ __forceinline__ float ema_elem(float t, float s, float m, float alpha) {
   return __fadd_rn(__fmul_rn(t, m), __fmul_rn(alpha, s));
@@ -235,34 +231,20 @@ __device__ __forceinline__ float ema_elem(float t, float s, float m, float alpha
 __global__ void __launch_bounds__(256)
 k_ema_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob, float m, float alpha) {
   const int b = blockIdx.x;
-  int lo = 0, hi = nprob - 1;                         // last pair whose first workgroup is <= b
-  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (wg_start[mid] <= b) lo = mid; else hi = mid - 1; }
+  const int lo = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)lo * 4;
   gf32* t = reinterpret_cast<gf32*>(d[0]);
   cgf32* s = reinterpret_cast<cgf32*>(d[1]);
-  const int64_t numel = d[2];
-  const int64_t e0 = (int64_t)(b - wg_start[lo]) * EMA_PER_WG;
-  if (d[3] & 1) {
-#pragma unroll
-    for (int i = 0; i < EMA_PER_WG / (256 * 4); ++i) {
-      const int64_t e = e0 + ((int64_t)i * 256 + threadIdx.x) * 4;
-      if (e + 4 <= numel) {
-        f32x4_t tv = *reinterpret_cast<cgf32x4*>(t + e);
-        const f32x4_t sv = *reinterpret_cast<cgf32x4*>(s + e);
+  group_span<EMA_PER_WG, 4>(
+      (int64_t)(b - wg_start[lo]) * EMA_PER_WG, d[2], d[3] & 1,
+      [&](int64_t e) {
+        f32x4_t tv = ld4(t + e);
+        const f32x4_t sv = ld4(s + e);
 #pragma unroll
         for (int k = 0; k < 4; ++k) tv[k] = ema_elem(tv[k], sv[k], m, alpha);
-        *reinterpret_cast<gf32x4*>(t + e) = tv;
-      } else {
-        for (int64_t k = e; k < numel; ++k) t[k] = ema_elem(t[k], s[k], m, alpha);
-      }
-    }
-  } else {
-#pragma unroll 4
-    for (int i = 0; i < EMA_PER_WG / 256; ++i) {
-      const int64_t k = e0 + (int64_t)i * 256 + threadIdx.x;
-      if (k < numel) t[k] = ema_elem(t[k], s[k], m, alpha);
-    }
-  }
+        st4(t + e, tv);
+      },
+      [&](int64_t k) { t[k] = ema_elem(t[k], s[k], m, alpha); });
 }
 
 // rows per workgroup of the ordered passes: the rows split evenly over the workgroups, rounded up to whole tiles
@@ -360,8 +342,7 @@ extern "C" int ss_mask_token_bwd(const void* g, int dtype, const uint8_t* mask, 
 
 extern "C" int ss_ema_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, float m, float alpha,
                             hipStream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
   SS_LAUNCH(k_ema_group, dim3((unsigned)total_workgroups), dim3(256), 0, stream, desc, wg_start, nprob, m, alpha);
   return SS_OK;
 }

@@ -15,7 +15,7 @@
 // (SQ_LDS_BANK_CONFLICT went from 48 % of the LDS cycles to 0).
 // Pipeline, phases, staggered wave rows and hazard rules: exactly gemm8.hip's (see its header).
 // GATHER: the (site, neighbour) ids of up to W8_CHUNK K-tiles live in LDS; longer shares are walked chunk by chunk.
-#include "common.h"
+#include "grouped.h"
 #include "../../include/scenesplat_hip.h"
 #include <stdlib.h>
 
@@ -346,13 +346,11 @@ k_wgrad8(const unsigned short* __restrict__ X, const unsigned short* __restrict_
 
 // Grouped nn.Linear weight gradients: ONE launch for many independent problems (the six identical blocks of a pooled
 // stage produce thirty weight gradients of 20-30 us each, latency-bound on 12-20 workgroups apiece).  desc: 8 int64 words
-// per problem = {x, dy, dW, dbias, m, k_in | n_out << 32, ntn | ntiles << 32, nshares | min_per << 32}; wg_start
-// (nprob + 1): first workgroup of every problem.
+// per problem = {x, dy, dW, dbias, m, k_in | n_out << 32, ntn | ntiles << 32, nshares | min_per << 32}.
 __global__ void __launch_bounds__(512)
 k_wgrad8_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob, int nprob_flags) {
   const int b = blockIdx.x;
-  int p = 0;
-  while (p + 1 < nprob && wg_start[p + 1] <= b) ++p;          // nprob <= 128: a scalar scan
+  const int p = group_owner(wg_start, nprob, b);
   const int64_t* d = desc + (int64_t)p * 8;
   const int64_t m = d[4];
   const uint64_t w5 = (uint64_t)d[5], w6 = (uint64_t)d[6], w7 = (uint64_t)d[7];
@@ -472,11 +470,11 @@ extern "C" int ss_linear_wgrad_group_plan(int64_t m, int k_in, int n_out, int64_
   return ss_linear_wgrad_group_plan2(m, k_in, n_out, 0, desc_words);
 }
 
-// desc (nprob, 8) int64 and wg_start (nprob + 1) int32 in DEVICE memory (see k_wgrad8_group); every dW / dbias zeroed.
+// desc as k_wgrad8_group reads it; every dW / dbias zeroed.
 extern "C" int ss_linear_wgrad_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups,
                                      hipStream_t stream) {
-  if (nprob <= 0 || total_workgroups <= 0) return SS_OK;
-  if (!desc || !wg_start || nprob > 128) return SS_ERR_ARG;
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_workgroups);
+  if (nprob > 128) return SS_ERR_ARG;
   // (the XCD-aware order is NOT applied to the Linear problems: in-process A/B of the whole step 36.79 ms with it, 36.58 without -- their
   // launches are ONE round of <= 256 workgroups, every tile of a run would be resident at once on neighbouring CUs of one XCD)
   SS_LAUNCH(k_wgrad8_group, dim3((unsigned)total_workgroups), dim3(512), 0, stream, desc, wg_start, nprob, 0);

@@ -4,87 +4,17 @@ PyTorch supplies device memory and the current HIP stream only; every call here 
 hand-written HIP kernel.  Operands are validated on the host (device, dtype, contiguity,
 shape) before any launch; a CPU tensor is an error -- there is no fallback path."""
 import ctypes
-import os
 
+import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, grouped
 from ._lib import check
 
 F32, BF16 = 0, 1
 ATTN_SIMT, ATTN_MFMA = 0, 1
 HAVE_MFMA_ATTN = True  # bf16 MFMA window attention (csrc/attention_mfma.hip)
 ORDER_IDS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
-
-
-_GROUP_WIDE_SHARES = os.environ.get("SS_WGRAD_GROUP_WIDE", "1") != "0"   # 0: plan every problem of a group as if it had the chip to itself (diagnostic A/B)
-_GROUP_KEEP = []      # (event, pinned sources, device copies) of grouped launches whose upload may still be in flight
-_GROUP_LOCK = __import__("threading").Lock()
-
-
-class DescriptorPool:
-    """Pinned host memory for the descriptors of grouped launches issued INSIDE a hipGraph capture (steady_state.py).
-    The captured host-to-device copy re-reads its source on every replay, so the source must live, unchanged, as long as
-    the graph does; and pinned memory cannot be allocated while a stream is capturing.  The pool is allocated before the
-    capture begins and owned by the captured step.
-
-    open_capture(device), called right after capture_begin, records ONE copy of the whole pool into a device mirror: a copy
-    node reads its source at REPLAY time, so the tables that the step writes into the pool later in the capture are all
-    uploaded by that single node (34 separate 5-us copies per step before)."""
-
-    def __init__(self, nbytes=1 << 20):
-        self.buf = torch.empty(int(nbytes), dtype=torch.uint8).pin_memory()
-        self.off = 0
-        self.device_side = []
-        self.mirror = None
-
-    def open_capture(self, device):
-        self.mirror = torch.empty(self.buf.numel(), dtype=torch.uint8, device=device)
-        self.mirror.copy_(self.buf, non_blocking=True)
-
-    def take(self, arr):
-        """-> (pinned host view holding arr, device view of the same bytes in the mirror | None)"""
-        nb = arr.nbytes
-        off = (self.off + 63) & ~63
-        if off + nb > self.buf.numel():
-            raise RuntimeError("descriptor pool of the captured step is full")
-        self.off = off + nb
-        view = self.buf[off:off + nb]
-        view.numpy()[:] = arr.reshape(-1).view("uint8")
-        host = view.view(_NP2T[arr.dtype.name]).view(arr.shape)
-        dev = None if self.mirror is None else self.mirror[off:off + nb].view(_NP2T[arr.dtype.name]).view(arr.shape)
-        return host, dev
-
-
-_NP2T = {"int64": torch.int64, "int32": torch.int32}
-CAPTURE_POOL = None   # a DescriptorPool while a capture is open
-
-
-def _upload_descriptors(desc, starts, dev):
-    """(descriptor rows, first-workgroup table) -> device tensors through pinned memory, without a stream sync."""
-    import numpy as np
-    starts = np.asarray(starts, dtype=np.int32)
-    if CAPTURE_POOL is not None and torch.cuda.is_current_stream_capturing():
-        (d_host, d_dev), (s_host, s_dev) = CAPTURE_POOL.take(desc), CAPTURE_POOL.take(starts)
-        if d_dev is None or d_dev.device != torch.device(dev):
-            d_dev, s_dev = d_host.to(dev, non_blocking=True), s_host.to(dev, non_blocking=True)
-            CAPTURE_POOL.device_side.append((d_dev, s_dev))
-        return d_dev, s_dev
-    d_host, s_host = torch.from_numpy(desc).pin_memory(), torch.from_numpy(starts).pin_memory()
-    d_dev, s_dev = d_host.to(dev, non_blocking=True), s_host.to(dev, non_blocking=True)
-    # the pinned sources must outlive their asynchronous copies: each upload is kept until an event recorded behind it has passed
-    # (a thread whose stream is capturing must not query events: it only appends)
-    ev = None
-    with _GROUP_LOCK:                         # (grouped launches may come from more than one host thread)
-        if not torch.cuda.is_current_stream_capturing():
-            ev = torch.cuda.Event(); ev.record()
-            while _GROUP_KEEP and _GROUP_KEEP[0][0] is not None and _GROUP_KEEP[0][0].query():
-                _GROUP_KEEP.pop(0)
-        _GROUP_KEEP.append((ev, d_host, s_host, d_dev, s_dev))
-        if len(_GROUP_KEEP) > 4096:           # (never reached in practice: a stalled stream would have to hold thousands of launches)
-            _GROUP_KEEP[0][0].synchronize() if _GROUP_KEEP[0][0] is not None else None
-            _GROUP_KEEP.pop(0)
-    return d_dev, s_dev
 
 
 def _p(t):
@@ -105,6 +35,17 @@ def _req(t, dtype=None, name="tensor", shape=None):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise RuntimeError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     return t
+
+
+def _req_dense_f32(t, n, dev, name):
+    """A tensor a grouped kernel may touch through its raw pointer: dense fp32, contiguous, n elements (None: any), on `dev`."""
+    _req(t, torch.float32, name)
+    if t.layout is not torch.strided or t.device != dev or (n is not None and t.numel() != n):
+        raise RuntimeError(f"{name}: expected a dense tensor" + (f" of {n} elements" if n is not None else "") + f" on {dev}")
+
+
+def _div_up(a, b):
+    return (a + b - 1) // b
 
 
 def dtype_code(t):
@@ -485,34 +426,29 @@ def linear_wgrad_into(x, dy, dw, db):
 def linear_wgrad_group(items):
     """ONE launch for many nn.Linear weight gradients.  items: list of (x (m,k) bf16, dy (m,n) bf16, dw (n,k) f32 ZEROED,
     db (n) f32 ZEROED | None).  Problems the pipeline kernel cannot take are run one by one."""
-    import numpy as np
     if not items:
         return
     dev = items[0][0].device
     desc = np.zeros((len(items), 8), dtype=np.int64)
-    starts = [0]
-    rows = []
+    counts = []
     # the CUs are shared out over the output tiles of the whole group (one round of workgroups for the launch)
-    launch_tiles = sum(lib().ss_linear_wgrad_tiles(x.shape[1], dy.shape[1]) for x, dy, _, _ in items) if _GROUP_WIDE_SHARES else 0
+    launch_tiles = sum(lib().ss_linear_wgrad_tiles(x.shape[1], dy.shape[1]) for x, dy, _, _ in items)
     for x, dy, dw, db in items:
         _req(x, torch.bfloat16, "x"); _req(dy, torch.bfloat16, "dy", (x.shape[0], dy.shape[1]))
         _req(dw, torch.float32, "dw", (dy.shape[1], x.shape[1]))
         if db is not None:
             _req(db, torch.float32, "db", (dy.shape[1],))
-        j = len(rows)
+        j = len(counts)
         nwg = lib().ss_linear_wgrad_group_plan2(x.shape[0], x.shape[1], dy.shape[1], launch_tiles, ctypes.c_void_p(desc[j].ctypes.data))
-        if nwg <= 0 or len(rows) >= 128:
+        if nwg <= 0 or j >= 128:
             linear_wgrad_into(x, dy, dw, db)
             continue
         desc[j, 0], desc[j, 1], desc[j, 2] = x.data_ptr(), dy.data_ptr(), dw.data_ptr()
         desc[j, 3] = db.data_ptr() if db is not None else 0
         desc[j, 4] = x.shape[0]
-        rows.append(j); starts.append(starts[-1] + nwg)
-    if not rows:
-        return
-    nprob = len(rows)
-    d_dev, s_dev = _upload_descriptors(desc[:nprob].copy(), starts, dev)
-    check(lib().ss_linear_wgrad_group(_p(d_dev), _p(s_dev), nprob, starts[-1], _stream()), "ss_linear_wgrad_group")
+        counts.append(nwg)
+    if counts:
+        grouped.launch("ss_linear_wgrad_group", desc[:len(counts)].copy(), grouped.starts(counts), dev)
 
 
 def linear_wgrad(x, dy, want_bias=False):
@@ -571,56 +507,45 @@ def ln_add_ln_fwd(x, t, gamma0, beta0, eps0, gamma1, beta1, eps1, h_dtype):
 
 def group_partial_sums(items):
     """ONE launch for many partial-sum reductions.  items: list of (part (K, nb, C) f32, dst (K, C) f32): dst = part.sum(1)."""
-    import numpy as np
     if not items:
         return
     dev = items[0][0].device
     desc = np.zeros((len(items), 4), dtype=np.int64)
-    starts = [0]
     per = lib().ss_group_partial_sums_outputs_per_workgroup()
     for j, (part, dst) in enumerate(items):
         K, nb, C = part.shape
         _req(part, torch.float32, "part"); _req(dst, torch.float32, "dst", (K, C))
         desc[j] = (part.data_ptr(), dst.data_ptr(), nb, C | ((K * C) << 32))
-        starts.append(starts[-1] + (K * C + per - 1) // per)
-    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
-    check(lib().ss_group_partial_sums(_p(d_dev), _p(s_dev), len(items), starts[-1], _stream()), "ss_group_partial_sums")
+    grouped.launch("ss_group_partial_sums", desc, grouped.starts(_div_up(desc[:, 3] >> 32, per)), dev)
 
 
 def subm_weight_mirror_group(pairs):
     """ONE launch: wt (cin, taps, cout) = tap-mirrored transpose of w (cout, taps, cin) for every (w, wt) bf16 pair."""
-    import numpy as np
     if not pairs:
         return
     dev = pairs[0][0].device
     desc = np.zeros((len(pairs), 5), dtype=np.int64)
-    starts = [0]
     tile = lib().ss_subm_weight_mirror_group_tile()
     for j, (w, wt) in enumerate(pairs):
         cout, taps, cin = w.shape
         _req(w, torch.bfloat16, "w"); _req(wt, torch.bfloat16, "wt", (cin, taps, cout))
         desc[j] = (w.data_ptr(), wt.data_ptr(), cout, taps, cin)
-        starts.append(starts[-1] + taps * ((cout + tile - 1) // tile) * ((cin + tile - 1) // tile))
-    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
-    check(lib().ss_subm_weight_mirror_group(_p(d_dev), _p(s_dev), len(pairs), starts[-1], _stream()), "ss_subm_weight_mirror_group")
+    starts = grouped.starts(desc[:, 3] * _div_up(desc[:, 2], tile) * _div_up(desc[:, 4], tile))
+    grouped.launch("ss_subm_weight_mirror_group", desc, starts, dev)
 
 
 def transpose16_group(pairs):
     """ONE launch: dst (cols, rows) = src (rows, cols)^T for every (src, dst) pair of 2-byte tensors (bf16 weight copies)."""
-    import numpy as np
     if not pairs:
         return
     dev = pairs[0][0].device
     desc = np.zeros((len(pairs), 4), dtype=np.int64)
-    starts = [0]
     for j, (src, dst) in enumerate(pairs):
         r, c = src.shape
         if src.element_size() != 2 or dst.element_size() != 2 or tuple(dst.shape) != (c, r) or not (src.is_contiguous() and dst.is_contiguous()):
             raise RuntimeError("transpose16_group: contiguous 2-byte (rows, cols) -> (cols, rows) pairs")
         desc[j] = (src.data_ptr(), dst.data_ptr(), r, c)
-        starts.append(starts[-1] + ((r + 63) // 64) * ((c + 63) // 64))
-    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
-    check(lib().ss_transpose16_group(_p(d_dev), _p(s_dev), len(pairs), starts[-1], _stream()), "ss_transpose16_group")
+    grouped.launch("ss_transpose16_group", desc, grouped.starts(_div_up(desc[:, 2], 64) * _div_up(desc[:, 3], 64)), dev)
 
 
 def ln_add_ln_bwd(g_xout, g_h, xout, t, stats, gamma0, gamma1, gx_dtype, gt_dtype, reduce=True):
@@ -1316,20 +1241,16 @@ def stream_capture_id(stream=None):
 
 def cast_bf16_group(srcs, dsts):
     """ONE launch: dst (bf16) = src (fp32) for every pair of equally shaped contiguous tensors (the weight shadows)."""
-    import numpy as np
     if not srcs:
         return
     dev = srcs[0].device
     per = lib().ss_cast_bf16_group_elems_per_workgroup()
     desc = np.zeros((len(srcs), 3), dtype=np.int64)
-    starts = [0]
     for j, (s, d) in enumerate(zip(srcs, dsts)):
         if s.dtype != torch.float32 or d.dtype != torch.bfloat16 or s.numel() != d.numel() or not (s.is_contiguous() and d.is_contiguous()):
             raise RuntimeError("cast_bf16_group: contiguous fp32 -> bf16 pairs of equal size")
         desc[j] = (s.data_ptr(), d.data_ptr(), s.numel())
-        starts.append(starts[-1] + (s.numel() + per - 1) // per)
-    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
-    check(lib().ss_cast_bf16_group(_p(d_dev), _p(s_dev), len(srcs), starts[-1], _stream()), "ss_cast_bf16_group")
+    grouped.launch("ss_cast_bf16_group", desc, grouped.starts(_div_up(desc[:, 2], per)), dev)
 
 
 # ---- optimizer step: global gradient norm + grouped AdamW update (csrc/optim.hip) ----------------------------------------------
@@ -1344,44 +1265,30 @@ def _norm_partials(dev, n):
     return buf
 
 
-def _optim_check(t, n, dev, name):
-    """A tensor a grouped optimizer kernel may touch through its raw pointer: dense fp32, contiguous, n elements, on `dev`."""
-    _req(t, torch.float32, name)
-    if t.layout is not torch.strided or t.device != dev or (n is not None and t.numel() != n):
-        raise RuntimeError(f"{name}: expected a dense tensor" + (f" of {n} elements" if n is not None else "") + f" on {dev}")
-
-
 def _optim_starts(numels):
-    per = lib().ss_optim_group_elems_per_workgroup()
-    starts = [0]
-    for n in numels:
-        starts.append(starts[-1] + (n + per - 1) // per)
-    if starts[-1] >= 2 ** 31:
-        raise RuntimeError("grouped optimizer launch: more than 2^31 workgroups")
-    return starts
+    """numels: the descriptor column of element counts"""
+    return grouped.starts(_div_up(numels, lib().ss_optim_group_elems_per_workgroup()))
 
 
 def grad_norm_group(grads, max_norm, record=None):
     """-> record (2,) fp32 on the device: [total_norm, coef] with total_norm the 2-norm over ALL of `grads` and
     coef = min(1, max_norm / (total_norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s arithmetic.  Two launches, no host read;
     the gradients are only read.  `record`: an existing (2,) fp32 tensor to write into."""
-    import numpy as np
     if record is not None:
         dev = _req(record, torch.float32, "record", (2,)).device
     else:
         dev = _req(grads[0], None, "grads[0]").device if len(grads) else torch.device("cuda", torch.cuda.current_device())
         record = torch.empty(2, dtype=torch.float32, device=dev)
     for j, g in enumerate(grads):
-        _optim_check(g, None, dev, f"grads[{j}]")
+        _req_dense_f32(g, None, dev, f"grads[{j}]")
     grads = [g for g in grads if g.numel()]                  # (an empty tensor adds nothing and owns no workgroup)
-    starts = _optim_starts([g.numel() for g in grads])
+    desc = np.empty((len(grads), 3), dtype=np.int64)
+    desc[:, 0], desc[:, 1] = [g.data_ptr() for g in grads], [g.numel() for g in grads]
+    desc[:, 2] = (desc[:, 0] & 15) == 0                      # bit 0: 16-byte lanes
+    starts = _optim_starts(desc[:, 1])
     partials = _norm_partials(dev, starts[-1])
     if grads:
-        desc = np.empty((len(grads), 3), dtype=np.int64)
-        desc[:, 0], desc[:, 1] = [g.data_ptr() for g in grads], [g.numel() for g in grads]
-        desc[:, 2] = (desc[:, 0] & 15) == 0                  # bit 0: 16-byte lanes
-        d_dev, s_dev = _upload_descriptors(desc, starts, dev)
-        check(lib().ss_grad_sqnorm_group(_p(d_dev), _p(s_dev), len(grads), starts[-1], _p(partials), _stream()), "ss_grad_sqnorm_group")
+        grouped.launch("ss_grad_sqnorm_group", desc, starts, dev, _p(partials))
     check(lib().ss_grad_norm_finish(_p(partials), starts[-1], float(max_norm), _p(record), _stream()), "ss_grad_norm_finish")
     return record
 
@@ -1390,7 +1297,6 @@ def adamw_group(rows, record=None):
     """ONE launch: the AdamW update of every row (p, g, m, v, scalars) with scalars = (1 - lr*wd, 1 - beta1, beta2, 1 - beta2,
     sqrt(1 - beta2^t), eps, lr / (1 - beta1^t)) computed by the caller in double.  p, m, v are updated in place, g is only read;
     `record` (from grad_norm_group) scales g by its clip coefficient on the fly, None means no clipping."""
-    import numpy as np
     if not len(rows):
         return
     dev = _req(rows[0][0], torch.float32, "rows[0].p").device
@@ -1398,22 +1304,19 @@ def adamw_group(rows, record=None):
         raise RuntimeError("record: must live on the parameters' device")
     for j, (p, g, m, v, s) in enumerate(rows):
         for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
-            _optim_check(t, p.numel(), dev, f"rows[{j}].{nm}")
+            _req_dense_f32(t, p.numel(), dev, f"rows[{j}].{nm}")
         if len(s) != 7:
             raise RuntimeError(f"rows[{j}]: 7 scalars per row")
     rows = [r for r in rows if r[0].numel()]
     if not rows:
         return
-    n = len(rows)
-    starts = _optim_starts([r[0].numel() for r in rows])
-    desc = np.zeros((n, 10), dtype=np.int64)
+    desc = np.zeros((len(rows), 10), dtype=np.int64)
     for k in range(4):
         desc[:, k] = [r[k].data_ptr() for r in rows]
     desc[:, 4] = [r[0].numel() for r in rows]
     desc[:, 5] = ((desc[:, 0] | desc[:, 1] | desc[:, 2] | desc[:, 3]) & 15) == 0        # bit 0: 16-byte lanes
     desc[:, 6:].view(np.float32)[:, :7] = np.asarray([r[4] for r in rows], dtype=np.float64)   # fp32 over the last four words
-    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
-    check(lib().ss_adamw_group(_p(d_dev), _p(s_dev), n, starts[-1], _p(record), _stream()), "ss_adamw_group")
+    grouped.launch("ss_adamw_group", desc, _optim_starts(desc[:, 4]), dev, _p(record))
 
 
 # ---- PDNorm prompt modulation of all PDNorm layers of a model: one grouped launch each way (csrc/pdnorm.hip) --------------------
@@ -1425,7 +1328,6 @@ class PDNormTable:
     to call (C, W, b, gamma, beta), built once and reused while the parameters stay where they are (`current`)."""
 
     def __init__(self, rows, context_channels):
-        import numpy as np
         if not rows:
             raise RuntimeError("pdnorm: an empty group has no table")
         self.cc = int(context_channels)
@@ -1435,16 +1337,14 @@ class PDNormTable:
             if w.dim() != 2 or w.shape[0] % 2 or w.shape[1] != self.cc:
                 raise RuntimeError(f"rows[{j}].W: expected (2C, {self.cc}), got {tuple(w.shape)}")
             c = w.shape[0] // 2
-            _optim_check(w, 2 * c * self.cc, self.dev, f"rows[{j}].W")
-            _optim_check(b, 2 * c, self.dev, f"rows[{j}].b")
+            _req_dense_f32(w, 2 * c * self.cc, self.dev, f"rows[{j}].W")
+            _req_dense_f32(b, 2 * c, self.dev, f"rows[{j}].b")
             for t, nm in ((g, "gamma"), (be, "beta")):
                 if t is not None:
-                    _optim_check(t, c, self.dev, f"rows[{j}].{nm}")
+                    _req_dense_f32(t, c, self.dev, f"rows[{j}].{nm}")
             self.widths.append(c)
         per = lib().ss_pdnorm_channels_per_workgroup()
-        self.starts = [0]
-        for c in self.widths:
-            self.starts.append(self.starts[-1] + (c + per - 1) // per)
+        self.starts = grouped.starts(_div_up(c, per) for c in self.widths)
         self.sig = self.signature(rows)
         self.desc = np.zeros((len(rows), PDNORM_WORDS), dtype=np.int64)
         self.desc[:, 0] = self.widths
@@ -1480,10 +1380,8 @@ def pdnorm_mod_fwd(context, tab):
     desc[:, 5] = base + 4 * tab.off[:-1]
     desc[:, 6] = base + 4 * (total + tab.off[:-1])
     desc[:, 7] = base + 4 * (2 * total + tab.off[:-1])
-    d_dev, s_dev = _upload_descriptors(desc, tab.starts, tab.dev)
     vec4 = int(tab.vec4 and context.data_ptr() % 16 == 0)
-    check(lib().ss_pdnorm_mod_fwd(_p(d_dev), _p(s_dev), len(tab.widths), tab.starts[-1], _p(context), tab.cc, vec4, _stream()),
-          "ss_pdnorm_mod_fwd")
+    grouped.launch("ss_pdnorm_mod_fwd", desc, tab.starts, tab.dev, _p(context), tab.cc, vec4)
     o = [int(x) for x in tab.off]
     geff = [out[o[l]:o[l + 1]] for l in range(len(tab.widths))]
     beff = [out[total + o[l]:total + o[l + 1]] for l in range(len(tab.widths))]
@@ -1498,11 +1396,11 @@ def pdnorm_mod_bwd(context, tab, ops, dgeff, dbeff, split_row=0):
     _pdnorm_context(context, tab)
     n = len(tab.widths)
     total = int(tab.off[-1])
-    _optim_check(ops, total, tab.dev, "ops")
+    _req_dense_f32(ops, total, tab.dev, "ops")
     for l in range(n):
         for t, nm in ((dgeff[l], "dgamma_eff"), (dbeff[l], "dbeta_eff")):
             if t is not None:
-                _optim_check(t, tab.widths[l], tab.dev, f"{nm}[{l}]")
+                _req_dense_f32(t, tab.widths[l], tab.dev, f"{nm}[{l}]")
     wtot = int(tab.w_off[-1])
     out = torch.empty(wtot + 4 * total, dtype=torch.float32, device=tab.dev)      # dW | db (2 per channel) | dgamma | dbeta
     partials = torch.empty(tab.starts[-1] * tab.cc, dtype=torch.float32, device=tab.dev)
@@ -1516,10 +1414,8 @@ def pdnorm_mod_bwd(context, tab, ops, dgeff, dbeff, split_row=0):
     desc[:, 11] = base + 4 * (wtot + 2 * tab.off[:-1])
     desc[:, 12] = [base + 4 * (wtot + 2 * total + int(tab.off[l])) if tab.affine[l][0] else 0 for l in range(n)]
     desc[:, 13] = [base + 4 * (wtot + 3 * total + int(tab.off[l])) if tab.affine[l][1] else 0 for l in range(n)]
-    d_dev, s_dev = _upload_descriptors(desc, tab.starts, tab.dev)
     vec4 = int(tab.vec4 and context.data_ptr() % 16 == 0 and base % 16 == 0)
-    check(lib().ss_pdnorm_mod_bwd(_p(d_dev), _p(s_dev), n, tab.starts[-1], _p(context), tab.cc, vec4, int(tab.starts[split_row]), _p(partials), _p(dcontext),
-                                  _stream()), "ss_pdnorm_mod_bwd")
+    grouped.launch("ss_pdnorm_mod_bwd", desc, tab.starts, tab.dev, _p(context), tab.cc, vec4, int(tab.starts[split_row]), _p(partials), _p(dcontext))
     o, wo = [int(x) for x in tab.off], [int(x) for x in tab.w_off]
     dW = [out[wo[l]:wo[l + 1]].view(2 * tab.widths[l], tab.cc) for l in range(n)]
     db = [out[wtot + 2 * o[l]:wtot + 2 * o[l + 1]] for l in range(n)]
@@ -1616,7 +1512,6 @@ def ema_group(teacher, student, m, cache=None):
     torch._foreach_add_(alpha=1 - m) does.  The caller bumps the version counters of `teacher` (the kernel writes through raw pointers).
     cache: a dict the caller keeps between calls; while every tensor stays where it was (same data pointers) the checked and uploaded
     descriptor table is reused, and a call is the pointer comparison plus the launch."""
-    import numpy as np
     if len(teacher) != len(student):
         raise RuntimeError("ema_group: one student tensor per teacher tensor")
     if not len(teacher):
@@ -1624,21 +1519,19 @@ def ema_group(teacher, student, m, cache=None):
     m = float(m)
     key = tuple(t.data_ptr() for t in teacher) + tuple(s.data_ptr() for s in student)
     if cache is not None and cache.get("key") == key:
-        d_dev, s_dev, n, total = cache["launch"]
-        check(lib().ss_ema_group(_p(d_dev), _p(s_dev), n, total, m, 1.0 - m, _stream()), "ss_ema_group")
+        grouped.relaunch("ss_ema_group", *cache["launch"], m, 1.0 - m)
         return
     dev = _req(teacher[0], torch.float32, "teacher[0]").device
     for j, (t, s) in enumerate(zip(teacher, student)):
-        _optim_check(t, None, dev, f"teacher[{j}]"); _optim_check(s, t.numel(), dev, f"student[{j}]")
+        _req_dense_f32(t, None, dev, f"teacher[{j}]"); _req_dense_f32(s, t.numel(), dev, f"student[{j}]")
     pairs = [(t, s) for t, s in zip(teacher, student) if t.numel()]
     if not pairs:
         return
-    starts = _optim_starts([t.numel() for t, _ in pairs])
     desc = np.zeros((len(pairs), 4), dtype=np.int64)
     desc[:, 0], desc[:, 1] = [t.data_ptr() for t, _ in pairs], [s.data_ptr() for _, s in pairs]
     desc[:, 2] = [t.numel() for t, _ in pairs]
     desc[:, 3] = ((desc[:, 0] | desc[:, 1]) & 15) == 0
-    d_dev, s_dev = _upload_descriptors(desc, starts, dev)
+    starts = _optim_starts(desc[:, 2])
+    tables = grouped.launch("ss_ema_group", desc, starts, dev, m, 1.0 - m)
     if cache is not None and not torch.cuda.is_current_stream_capturing():
-        cache["key"], cache["launch"] = key, (d_dev, s_dev, len(pairs), starts[-1])
-    check(lib().ss_ema_group(_p(d_dev), _p(s_dev), len(pairs), starts[-1], m, 1.0 - m, _stream()), "ss_ema_group")
+        cache["key"], cache["launch"] = key, (tables, starts[-1])

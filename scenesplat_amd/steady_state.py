@@ -28,6 +28,7 @@ import warnings
 import torch
 
 from . import functional as SF
+from . import grouped
 from . import native as nv
 from .plan import HOST_SYNC_GATE
 
@@ -208,13 +209,13 @@ class SteadyStateStep:
         gc.collect()      # unreachable autograd graphs of earlier steps hold AccumulateGrad nodes of the default stream
         for p in self.params:
             p.grad = None
-        cap.keep = nv.DescriptorPool()
+        cap.keep = grouped.DescriptorPool()
         cap.graph = torch.cuda.CUDAGraph()
         cap.graph2 = torch.cuda.CUDAGraph() if self.tail is not None else None
         main = torch.cuda.current_stream()
         side = torch.cuda.Stream()
         torch.cuda.synchronize()
-        nv.CAPTURE_POOL = cap.keep
+        grouped.CAPTURE_POOL = cap.keep
         try:
             # capture_begin / capture_end by hand (not `with torch.cuda.graph`).  thread_local error mode: HIP calls of OTHER
             # threads (a pin-memory thread, a plan build on its own stream) no longer invalidate this capture.  When the step
@@ -259,7 +260,7 @@ class SteadyStateStep:
                         raise CaptureInvalidated("hipGraph capture (second graph) invalidated by a call inside the step")
                     cap.graph2.capture_end()
         finally:
-            nv.CAPTURE_POOL = None
+            grouped.CAPTURE_POOL = None
         main.wait_stream(side)
         cap.grads = [(p, p.grad) for p in self.params if p.grad is not None]
         return cap

@@ -178,7 +178,8 @@ def test_grouped_modulation_argument_handling():
     out = torch.full((3 * 4,), 7.0, device="cuda")
     desc = tab.desc.copy()
     desc[:, 5], desc[:, 6], desc[:, 7] = out.data_ptr(), out.data_ptr() + 16, out.data_ptr() + 32
-    d_dev, s_dev = nv._upload_descriptors(desc, tab.starts, tab.dev)
+    from scenesplat_amd import grouped
+    d_dev, s_dev = grouped._upload_descriptors(desc, tab.starts, tab.dev)
     lib, p, st = nv.lib(), nv._p, nv._stream()
     null = ctypes.c_void_p(0)
     assert lib.ss_pdnorm_mod_fwd(p(d_dev), p(s_dev), 0, 0, p(c32), 24, 0, st) == 0                # L = 0: SS_OK, no launch
