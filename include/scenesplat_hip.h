@@ -103,6 +103,18 @@ int ss_window_attn_bwd(const void* qkv, const void* out, const void* dout, const
 int ss_cast_bf16_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
 int ss_cast_bf16_group_elems_per_workgroup(void);
 
+/* Scene ingest: every asset of a packed scene arena -> its output tensor, with numpy's astype / clip / reshape / [:, column] values
+ * bit for bit (replaces one host conversion and one upload per .npy file of a dataset sample).
+ * desc: 8 words {src pointer, dst pointer, n_out elements, src dtype | dst dtype << 8 | flags << 16, src row stride, column (both in
+ * elements; read with flag 4 only: out[k] = src[k * stride + column]), lo, hi (fp32 bit patterns in the low 32 bits; dst f32 only)}.
+ * dtype codes: 0 f64, 1 f32, 2 f16, 3 u8, 4 i8, 5 i16, 6 i32, 7 i64, 8 bool.  flags: 1 has_lo, 2 has_hi, 4 pick_column.
+ * Pairs: any source -> f32 (then out = v < lo ? lo : v > hi ? hi : v, so NaN stays and -0.0 passes lo = 0); f32 | f16 -> f16
+ * (round to nearest even, overflow to inf, subnormals kept); u8 | i8 | i16 | i32 | i64 | bool -> i32 (wraps) and -> bool (any bit
+ * set); equal dtypes: a copy.  Any other pair writes nothing (the Python wrapper refuses it).  16-byte source loads when src and dst
+ * are 16-byte aligned.  A workgroup owns ss_ingest_group_elems_per_workgroup() consecutive output elements. */
+int ss_ingest_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
+int ss_ingest_group_elems_per_workgroup(void);
+
 /* ---- optimizer step: global gradient norm + AdamW update of all tensors of all parameter groups (replaces
  * torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step, pointcept/engines/train.py:196-232).  Grouped launches as above:
  * a workgroup owns ss_optim_group_elems_per_workgroup() elements; flags bit 0 = every pointer of the row is 16-byte aligned

@@ -47,6 +47,8 @@ PROTOTYPES = {
     "ss_stream_capture_id": (ctypes.c_ulonglong, [c_p]),
     "ss_cast_bf16_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "ss_cast_bf16_group_elems_per_workgroup": (c_i, []),
+    "ss_ingest_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),
+    "ss_ingest_group_elems_per_workgroup": (c_i, []),
     "ss_optim_group_elems_per_workgroup": (c_i, []),
     "ss_grad_sqnorm_group": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "ss_grad_norm_finish": (c_i, [c_p, c_i, c_f, c_p, c_p]),

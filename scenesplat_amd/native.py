@@ -1253,8 +1253,100 @@ def cast_bf16_group(srcs, dsts):
     grouped.launch("ss_cast_bf16_group", desc, grouped.starts(_div_up(desc[:, 2], per)), dev)
 
 
+# ---- scene ingest: every asset of a packed scene arena -> its output tensor in one grouped launch (csrc/ingest.hip) ----------------
+INGEST_CODES = {"float64": 0, "float32": 1, "float16": 2, "uint8": 3, "int8": 4, "int16": 5, "int32": 6, "int64": 7, "bool": 8}
+INGEST_HAS_LO, INGEST_HAS_HI, INGEST_PICK = 1, 2, 4
+INGEST_ALIGN = 256          # arena offsets: an asset that needs no conversion is handed out as a view of the arena
+_INGEST_INT = ("uint8", "int8", "int16", "int32", "int64", "bool")
+
+
+def ingest_pair_on_device(src, dst):
+    """Does the kernel convert numpy dtype `src` to `dst` itself?  (f64 -> f16 would round twice on the way through f32, and a
+    float -> int / bool cast has numpy's own corner cases: those are converted on the host before packing.)"""
+    if src not in INGEST_CODES or dst not in INGEST_CODES:
+        return False
+    return src == dst or dst == "float32" or (dst == "float16" and src == "float32") or (dst in ("int32", "bool") and src in _INGEST_INT)
+
+
+def ingest_plan(arrays, rules):
+    """The launch of one scene as a pure host function.  arrays: {stored name: ndarray}, in packing order.  rules: {stored name:
+    dict(name=output key, dtype=target numpy dtype name | None (as stored), lo=, hi= (clip bounds of an f32 target), shape="keep" |
+    "flat" | "col1" (n, 1) | "column" ([:, column]) | "column_or_flat" (the column of a 2-d array, else flattened), column=0)}; a
+    name without a rule is passed through as stored.
+    -> (desc (k, 8) int64: the rows of ss_ingest_group with word 0 = the BYTE OFFSET of the asset in the arena and word 1 = 0 (the
+        caller adds the arena's address and fills in the outputs'),
+        offsets {stored name: byte offset, a multiple of INGEST_ALIGN; "" : the arena's size},
+        specs [dict(stored, name, dtype, shape, alias (the arena's bytes ARE the output), array (what to pack))], one per row,
+        fallback [stored names converted with numpy on the host])."""
+    desc = np.zeros((len(arrays), 8), dtype=np.int64)
+    offsets, specs, fallback, off = {}, [], [], 0
+    for j, (stored, arr) in enumerate(arrays.items()):
+        rule = rules.get(stored, {})
+        arr = np.asarray(arr)
+        if arr.dtype.byteorder == ">" or not arr.flags.c_contiguous:
+            arr = np.ascontiguousarray(arr.astype(arr.dtype.newbyteorder("=")))
+        src = arr.dtype.name
+        dst = rule.get("dtype") or src
+        lo, hi = rule.get("lo"), rule.get("hi")
+        if (lo is not None or hi is not None) and dst != "float32":
+            raise ValueError(f"ingest_plan: '{stored}': a clip needs a float32 target")
+        if dst not in INGEST_CODES:
+            raise TypeError(f"ingest_plan: '{stored}': dtype {dst} has no device form")
+        if not ingest_pair_on_device(src, dst):
+            with np.errstate(over="ignore", invalid="ignore"):
+                arr = arr.astype(dst)                  # numpy's own conversion; the device pair becomes dst -> dst
+            fallback.append(stored)
+            src = dst
+        shape_rule = rule.get("shape", "keep")
+        flags = (INGEST_HAS_LO if lo is not None else 0) | (INGEST_HAS_HI if hi is not None else 0)
+        stride = col = 0
+        if shape_rule == "column_or_flat":
+            shape_rule = "column" if arr.ndim == 2 else "flat"
+        if shape_rule == "column":
+            if arr.ndim != 2:
+                raise IndexError(f"ingest_plan: '{stored}': [:, {rule.get('column', 0)}] of a {arr.ndim}-d array")
+            stride, col = arr.shape[1], int(rule.get("column", 0)) % max(arr.shape[1], 1)
+            shape, flags = (arr.shape[0],), flags | INGEST_PICK
+        elif shape_rule == "flat":
+            shape = (arr.size,)
+        elif shape_rule == "col1":
+            shape = (arr.size, 1)
+        elif shape_rule == "keep":
+            shape = tuple(arr.shape)
+        else:
+            raise ValueError(f"ingest_plan: shape rule '{shape_rule}'")
+        n_out = int(np.prod(shape, dtype=np.int64))
+        desc[j] = (off, 0, n_out, INGEST_CODES[src] | (INGEST_CODES[dst] << 8) | (flags << 16), stride, col,
+                   int(np.float32(0.0 if lo is None else lo).view(np.uint32)), int(np.float32(0.0 if hi is None else hi).view(np.uint32)))
+        offsets[stored] = off
+        specs.append(dict(stored=stored, name=rule.get("name", stored), dtype=dst, shape=shape, alias=(src == dst and flags == 0), array=arr))
+        off = _div_up(off + arr.nbytes, INGEST_ALIGN) * INGEST_ALIGN
+    offsets[""] = off
+    return desc, offsets, specs, fallback
+
+
+def ingest_group(desc, dev):
+    """ONE launch of ss_ingest_group over the rows of `desc` ((k, 8) int64 with real device addresses in words 0 and 1)."""
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    if desc.ndim != 2 or desc.shape[1] != 8:
+        raise RuntimeError("ingest_group: desc must be (k, 8) int64")
+    if desc.shape[0] == 0:
+        return
+    names = {v: k for k, v in INGEST_CODES.items()}
+    for word, n_out, flags in zip(desc[:, 3].tolist(), desc[:, 2].tolist(), (desc[:, 3] >> 16).tolist()):
+        s, d = names.get(word & 0xff), names.get((word >> 8) & 0xff)
+        if s is None or d is None or not ingest_pair_on_device(s, d):
+            raise RuntimeError(f"ingest_group: no device conversion {s} -> {d} (convert on the host before packing)")
+        if n_out < 0 or ((flags & (INGEST_HAS_LO | INGEST_HAS_HI)) and d != "float32"):
+            raise RuntimeError("ingest_group: negative size, or a clip on a target that is not float32")
+    if ((desc[:, 2] > 0) & ((desc[:, 0] == 0) | (desc[:, 1] == 0))).any():
+        raise RuntimeError("ingest_group: null pointer in a non-empty problem")
+    per = lib().ss_ingest_group_elems_per_workgroup()
+    grouped.launch("ss_ingest_group", desc, grouped.starts(_div_up(desc[:, 2], per)), dev)
+
+
 # ---- optimizer step: global gradient norm + grouped AdamW update (csrc/optim.hip) ----------------------------------------------
-_NORM_PARTIALS = {}     # device -> fp64 partial sums of the norm kernel, one per workgroup (grown on demand, reused every step)
+_NORM_PARTIALS = {}    # device -> fp64 partial sums of the norm kernel, one per workgroup (grown on demand, reused every step)
 
 
 def _norm_partials(dev, n):

@@ -1,5 +1,5 @@
 """Host-side mirror of the pointcept interfaces the hot path sits behind (registries,
-``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, ``PDNorm`` / ``PPT-v1m2``, trainer/hook API, the training transforms, the open-vocabulary tester)."""
+``Point``, ``PT-v3m1``, ``LangPretrainer`` + criteria, ``DefaultSegmentorV2`` + criteria, ``PDNorm`` / ``PPT-v1m2``, trainer/hook API, the training transforms, the open-vocabulary tester, the datasets and device loaders)."""
 from .registry import HOOKS, LOSSES, MODELS, MODULES, PRETRAINERS, TESTERS, TRAINERS, TRANSFORMS, Registry, build_model  # noqa: F401
 from .structure import Point  # noqa: F401
 from . import ptv3  # noqa: F401  (registers PT-v3m1)
@@ -21,3 +21,7 @@ from . import ssl  # noqa: F401  (registers PT-v3m1-simdino and DefaultContrasti
 from .ssl import (CosinePatchLoss, CosineScheduler, DefaultContrastiverSimDinoV2, DINOHead, MCRLoss,  # noqa: F401
                   PointTransformerV3_SIMDINO)
 from .engine import DefaultSSLPreTrainer  # noqa: F401
+from . import datasets  # noqa: F401  (registers the dataset classes in DATASETS)
+from .datasets import (DATASETS, ConcatDataset, DefaultDataset, DeviceLoader, GenericGSDataset, HoliCityGSDataset,  # noqa: F401
+                       KITTI360GSDataset, Matterport3D_160_GSDataset, Matterport3DGSDataset, ScanNet200GSDataset, ScanNetGSDataset,
+                       ScanNetPPGSDataset, build_dataset, build_test_loader, build_train_loader, build_val_loader)
