@@ -3,9 +3,10 @@
 // Replaces the O(m n) brute-force scan of ss_knn_query (libs/pointops/src/knn_query/knn_query_cuda_kernel.cu:60-104 is the same
 // scan) where it matters: the zero-shot evaluator's neighbour voting (pointcept/engines/hooks/evaluator.py:697-739,
 // pointcept/utils/misc.py:54-95: cKDTree.query(k = 25) over ~10^6 valid Gaussians = 10^12 distance evaluations brute force).
-// Same result as the brute-force kernel -- the k nearest candidates of the query's batch element, ascending, -1 / 1e10 padding,
-// the SAME fp32 distance expression (po_dist2) -- found by expanding rings of grid cells around the query until the k-th best
-// distance is provably inside the searched region.
+// Same result as the brute-force kernel -- the k smallest (distance, index) pairs of the query's batch element, ascending (equal
+// distances: the smaller index first, also ACROSS the k-th place), -1 / 1e10 padding, the SAME fp32 distance expression
+// (po_dist2) -- found by expanding rings of grid cells around the query until the k-th best distance is provably inside the
+// searched region.
 //
 //   build   cell key = batch << 48 | cx << 32 | cy << 16 | cz   (cell = floor((p - origin) / h), 16 bits per axis)
 //           stable radix argsort of the keys (ss_argsort_i64, the plan's sort) -> points in cell order, copied next to each other
@@ -132,19 +133,23 @@ __device__ __forceinline__ void kg_merge64(float& bd, int& bi, float cd, int ci,
   if (lane >= k) { bd = KG_INF; bi = -1; }
 }
 
-// one candidate batch: d2 / oi per lane (act = the lane holds one)
+// one candidate batch: d2 / oi per lane (act = the lane holds one).  A candidate is admitted when it sorts before the k-th entry in
+// the list's own order (distance, then index): candidates arrive in ring and cell order, so one that is exactly as far as the k-th
+// entry but has the smaller index must still replace it.  An unfilled list has the threshold (KG_INF, -1), which every finite
+// candidate sorts before.
 __device__ __forceinline__ void kg_offer(float& bd, int& bi, float d2, int oi, bool act, int lane, int k) {
-  const float thr = __shfl(bd, k - 1, 64);
-  unsigned long long m = __ballot(act && d2 < thr);
+  const float thr_d = __shfl(bd, k - 1, 64); const int thr_i = __shfl(bi, k - 1, 64);
+  const bool in = act && kg_less(d2, oi, thr_d, thr_i);
+  unsigned long long m = __ballot(in);
   if (!m) return;
   if (__popcll(m) > 6) {
-    kg_merge64(bd, bi, (act && d2 < thr) ? d2 : KG_INF, (act && d2 < thr) ? oi : -1, lane, k);
+    kg_merge64(bd, bi, in ? d2 : KG_INF, in ? oi : -1, lane, k);
     return;
   }
   while (m) {
     const int j = __builtin_ctzll(m); m &= m - 1;
     const float cd = __shfl(d2, j, 64); const int ci = __shfl(oi, j, 64);
-    if (!(cd < __shfl(bd, k - 1, 64))) continue;
+    if (!kg_less(cd, ci, __shfl(bd, k - 1, 64), __shfl(bi, k - 1, 64))) continue;
     // position = number of list entries that sort before the candidate
     const int pos = __popcll(__ballot(kg_less(bd, bi, cd, ci)));
     const float ud = __shfl_up(bd, 1, 64); const int ui = __shfl_up(bi, 1, 64);
@@ -182,7 +187,8 @@ k_kg_query(int m, int k, const float* __restrict__ new_xyz, const int32_t* __res
   for (int r = r0; r <= r1 && !done; ++r) {
     if (r - r0 > KG_RING_MAX) {
       // sparse neighbourhood: scan the rest of the batch element wave-wide.  Points of rings < r were offered already; offering
-      // them again would duplicate entries, so they are skipped by their cell distance.
+      // them again would duplicate entries, so they are skipped by their cell distance (the same clamped cell the build keyed
+      // them by).  No point is ever offered twice, so kg_offer never meets a candidate equal to a list entry in (distance, index).
       for (int p0 = seg0; p0 < seg1; p0 += 64) {
         const int p = p0 + lane; const bool act = p < seg1;
         float d2 = KG_INF; int oi = -1; bool fresh = false;

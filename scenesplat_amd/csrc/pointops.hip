@@ -130,7 +130,7 @@ __global__ void k_ball_query(int m, int nsample, float min2, float max2, const f
     float d2 = dx * dx + dy * dy + dz * dz;
     if (d2 <= 1e-5f || (d2 >= min2 && d2 < max2)) { cd[num] = d2; ci[num] = i; ++num; }
   }
-  // heapify + heap sort ascending (ties keep no particular order, as in any heap sort)
+  // heapify + heap sort ascending by (distance, index): po_greater is a total order, so equal distances come out smaller index first
   for (int r = num / 2 - 1; r >= 0; --r) heap_down<0>(cd, ci, r, num);
   for (int i = num - 1; i > 0; --i) {
     float td = cd[0]; cd[0] = cd[i]; cd[i] = td;
