@@ -2,9 +2,12 @@
  *
  * Drop-in boundary for the native ops behind SceneSplat's PTv3 hot path.  Every entry point
  * takes raw DEVICE pointers, explicit sizes and a HIP stream, returns an int status
- * (SS_OK = 0), allocates nothing, keeps no global state and is re-entrant per stream; the
- * caller owns all memory (outputs and workspaces; sizes from the *_workspace_bytes queries).
- * No torch types appear here.  Reference interfaces replaced (paths under /root/reference):
+ * (SS_OK = 0), allocates nothing and is re-entrant per stream; the caller owns all memory
+ * (outputs and workspaces; sizes from the *_workspace_bytes queries).  It keeps no global state
+ * except process-wide kernel-choice switches: the flag ss_wgrad_set_xcd_order sets, and the
+ * environment variables SS_WGRAD_XCD_TRIPLE, SS_WGRAD_MINPER, SS_CONV_PIPE, SS_WGRAD_PIPE,
+ * SS_ATTN_FWD32, SS_ATTN_FWD_NQ and SS_ATTN_DO_INPLACE, each read once, at the first call that
+ * consults it.  No torch types appear here.  Reference interfaces replaced (paths under /root/reference):
  *
  *   ss_serialize_encode / ss_argsort_i64      pointcept/models/utils/structure.py:81-92
  *                                             (encode(): utils/serialization/default.py:8-24)
@@ -45,6 +48,8 @@ typedef struct ihipStream_t* ss_stream_t; /* == hipStream_t */
 enum { SS_ORDER_Z = 0, SS_ORDER_Z_TRANS = 1, SS_ORDER_HILBERT = 2, SS_ORDER_HILBERT_TRANS = 3 };
 enum { SS_DTYPE_F32 = 0, SS_DTYPE_BF16 = 1 };
 enum { SS_ATTN_SIMT = 0, SS_ATTN_MFMA = 1 };
+/* the int status every entry point returns: 0 = ok, 1 bad argument, 2 launch failed, 3 workspace too small */
+enum { SS_OK = 0, SS_ERR_ARG = 1, SS_ERR_LAUNCH = 2, SS_ERR_WORKSPACE = 3 };
 
 int ss_version(void);
 
@@ -158,7 +163,7 @@ int ss_pdnorm_mod_bwd(const int64_t* table, const int32_t* wg_start, int num_lay
 int ss_row_keep_scales(const int64_t* seed, const float* keep, float* out, int64_t n, ss_stream_t stream);
 
 /* ---- exact-erf GELU of the MLP (ptv3:225-248, nn.GELU()) on flat arrays ---------------------------------------
- * dy == NULL: out = gelu(x); else out = dy * gelu'(x).  dtype SS_F32 | SS_BF16 (math in fp32, one rounding); 16-byte aligned. */
+ * dy == NULL: out = gelu(x); else out = dy * gelu'(x).  dtype SS_DTYPE_F32 | SS_DTYPE_BF16 (math in fp32, one rounding); 16-byte aligned. */
 int ss_gelu(const void* x, const void* dy, void* out, int64_t numel, int dtype, ss_stream_t stream);
 
 /* ---- runtime queries -------------------------------------------------------------------- */

@@ -3,193 +3,60 @@
 Loading fails loudly: there is no CPU fallback behind these symbols."""
 import ctypes
 import os
+import re
 
 # torch first: PyTorch-ROCm ships its own libamdhip64; it must be the HIP runtime of the process
 # before this library (linked against the same soname) is mapped, or kernels and streams would
 # belong to two different runtimes and every launch fails.
 import torch  # noqa: F401
 
+from . import build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libscenesplat_hip.so")
 
-c_p = ctypes.c_void_p
-c_i = ctypes.c_int
-c_i64 = ctypes.c_int64
-c_f = ctypes.c_float
-c_sz = ctypes.c_size_t
+# C types of the header -> ctypes; anything with a `*` travels as c_void_p (it takes None, ints and the ctypes arrays of host values)
+_CTYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+           "size_t": ctypes.c_size_t, "unsigned long long": ctypes.c_ulonglong, "float": ctypes.c_float,
+           "ss_stream_t": ctypes.c_void_p}
+_DECL = re.compile(r"([\w\s]+?)\b(ss_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
 
-# name -> (restype, argtypes); must list every symbol include/scenesplat_hip.h declares
-PROTOTYPES = {
-    "ss_version": (c_i, []),
-    "ss_serialize_encode": (c_i, [c_p, c_p, c_i64, c_i, ctypes.POINTER(c_i), c_i, c_p, c_p]),
-    "ss_offsets_to_batch": (c_i, [c_p, c_i, c_i64, c_p, c_p]),
-    "ss_count_duplicates": (c_i, [c_p, c_i64, c_p, c_p]),
-    "ss_grid_coord_max": (c_i, [c_p, c_i64, c_p, c_p]),
-    "ss_argsort_workspace_bytes": (c_sz, [c_i64, c_i]),
-    "ss_argsort_i64": (c_i, [c_p, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "ss_pool_partition_workspace_bytes": (c_sz, [c_i64]),
-    "ss_pool_partition": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "ss_pool_level_attrs": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
-    "ss_batch_offsets": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p]),
-    "ss_window_index": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i64, c_p, c_p, c_p]),
-    "ss_window_attn_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p]),
-    "ss_window_attn_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i, c_i, c_i]),
-    "ss_window_attn_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i, c_f, c_i, c_i,
-                                 c_p, c_p, c_sz, c_p]),
-    "ss_window_attn_rpe_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_i,
-                                     c_p, c_p, c_p]),
-    "ss_window_attn_rpe_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "ss_window_attn_rpe_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i, c_f, c_i, c_i,
-                                     c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "ss_gelu": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p]),
-    "ss_row_keep_scales": (c_i, [c_p, c_p, c_p, c_i64, c_p]),
-    "ss_stream_capture_status": (c_i, [c_p]),
-    "ss_stream_capture_id": (ctypes.c_ulonglong, [c_p]),
-    "ss_cast_bf16_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),
-    "ss_cast_bf16_group_elems_per_workgroup": (c_i, []),
-    "ss_ingest_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),
-    "ss_ingest_group_elems_per_workgroup": (c_i, []),
-    "ss_optim_group_elems_per_workgroup": (c_i, []),
-    "ss_grad_sqnorm_group": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
-    "ss_grad_norm_finish": (c_i, [c_p, c_i, c_f, c_p, c_p]),
-    "ss_adamw_group": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
-    "ss_pdnorm_channels_per_workgroup": (c_i, []),
-    "ss_pdnorm_mod_fwd": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p]),
-    "ss_pdnorm_mod_bwd": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
-    "ss_linear_fwd_headmajor": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_f, c_p]),
-    "ss_headmajor_pack": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_i, c_i, c_f, c_p]),
-    "ss_window_attn_hm_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i, c_p, c_p, c_p]),
-    "ss_window_attn_hm_bwd_workspace_bytes": (c_sz, [c_i64, c_i64, c_i, c_i]),
-    "ss_window_attn_hm_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_i, c_f, c_p, c_p, c_sz, c_p]),
-    "ss_subm_rulebook": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_i, c_i, c_p, c_p]),
-    "ss_subm_conv_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),
-    "ss_stream_create_cu_mask": (c_i, [c_i, c_p, c_p]),
-    "ss_ln_add_ln_fwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_f, c_p, c_p, c_f, c_p, c_p, c_i, c_p, c_i64, c_i, c_p]),
-    "ss_ln_add_ln_bwd": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_i64, c_i, c_i, c_p]),
-    "ss_segment_minmax": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_segment_minmax_bwd": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),
-    "ss_subm_rulebook_table_size": (c_i64, [c_i64]),
-    "ss_subm_rulebook_hashed": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p, c_p, ctypes.c_size_t, c_p]),
-    "ss_subm_tap_mask_keys": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p, c_p]),
-    "ss_subm_weight_mirror": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
-    "ss_subm_im2col": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i64, c_p]),
-    "ss_gemm8_ok": (c_i, [c_i64, c_i, c_i, c_i]),
-    "ss_subm_conv_fwd_pipe": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),
-    "ss_linear_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_wgrad_xcd_order": (c_i, []),
-    "ss_wgrad_set_xcd_order": (c_i, [c_i]),
-    "ss_wgrad8_ok": (c_i, [c_i64, c_i, c_i, c_i]),
-    "ss_subm_conv_wgrad_pipe": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_linear_wgrad": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),
-    "ss_linear_wgrad_group_plan": (c_i, [c_i64, c_i, c_i, c_p]),
-    "ss_linear_wgrad_tiles": (c_i, [c_i, c_i]),
-    "ss_linear_wgrad_group_plan2": (c_i, [c_i64, c_i, c_i, c_i, c_p]),
-    "ss_linear_wgrad_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),
-    "ss_subm_conv_splits": (c_i, [c_i64, c_i, c_i]),
-    "ss_subm_conv_fwd_splitk": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),
-    "ss_subm_block_lists": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p]),
-    "ss_subm_conv_wgrad": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_subm_conv_fwd_pipe_walk": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),
-    "ss_subm_conv_fwd_uses_pipe": (c_i, [c_i64, c_i, c_i, c_i]),
-    "ss_subm_conv_fwd_walk": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),
-    "ss_subm_conv_wgrad_pipe_walk": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_subm_conv_wgrad_uses_pipe": (c_i, [c_i64, c_i, c_i, c_i]),
-    "ss_subm_conv_wgrad_walk": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_subm_f32_ok": (c_i, [c_i, c_i]),
-    "ss_subm_f32_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_subm_f32_dgrad_dup": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_dup_fold_rows": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),
-    "ss_dup_zero_rows": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_p]),
-    "ss_subm_f32_wgrad": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p]),
-    "ss_add_layernorm_fwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_f, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i64, c_i, c_p]),
-    "ss_add_layernorm_bwd_blocks": (c_i, [c_i64]),
-    "ss_block_tail_rows": (c_i, []),
-    "ss_block_tail_bwd_blocks": (c_i, [c_i64]),
-    "ss_block_tail_fwd": (c_i, [c_p] * 10 + [c_i, c_p, c_p, c_f] + [c_p] * 8 + [c_i64, c_i, c_p]),
-    "ss_block_tail_bwd": (c_i, [c_p] * 18 + [c_i64, c_i, c_i, c_p]),
-    "ss_group_partial_sums_outputs_per_workgroup": (c_i, []),
-    "ss_group_partial_sums": (c_i, [c_p, c_p, c_i, c_i, c_p]),
-    "ss_transpose16_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),
-    "ss_subm_weight_mirror_group_tile": (c_i, []),
-    "ss_subm_weight_mirror_group": (c_i, [c_p, c_p, c_i, c_i, c_p]),
-    "ss_add_layernorm_bwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p,
-                                   c_i64, c_i, c_i, c_p]),
-    "ss_col_stats": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),
-    "ss_bn_stats_finish": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_bn_bwd_finish": (c_i, [c_p, c_i, c_i, c_i64, c_p, c_p, c_p]),
-    "ss_bn_act_fwd": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i64, c_i, c_p]),
-    "ss_bn_act_bwd_reduce": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i64, c_i, c_i, c_p]),
-    "ss_bn_act_bwd_apply": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i64, c_i, c_p]),
-    "ss_feat_text_scan": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "ss_lang_head_blocks": (c_i, [c_i64]),
-    "ss_lang_head_fwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i64, c_i, c_p]),
-    "ss_lang_head_bwd": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_i64, c_i, c_p]),
-    "ss_seg_loss_workspace_bytes": (c_sz, [c_i64, c_i]),
-    "ss_seg_loss_fwd": (c_i, [c_p, c_i, c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "ss_seg_loss_bwd": (c_i, [c_p, c_i, c_p, c_i64, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_seg_iou": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_i64, c_p, c_p]),
-    "ss_gather_rows": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_p]),
-    "ss_scatter_rows": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_p]),
-    "ss_gather_add_rows": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p]),
-    "ss_segment_reduce": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_segment_bcast": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_i, c_p]),
-    "ss_aug_bbox_blocks": (c_i, [c_i64]),
-    "ss_aug_bbox": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p]),
-    "ss_aug_gaussians": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, ctypes.c_uint64, c_p]),
-    "ss_aug_elastic": (c_i, [c_p, c_i64, c_p, c_i, c_i, c_i, c_p, c_f, c_f, c_p]),
-    "ss_aug_color": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_f, c_p, c_f, c_p, ctypes.c_uint64, c_i, c_p]),
-    "ss_voxel_pick_labelled": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p]),
-    "ss_color_chain_blocks": (c_i, [c_i64]),
-    "ss_color_chain": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "ss_voxel_blur_table_size": (c_i64, [c_i64]),
-    "ss_voxel_blur_workspace_bytes": (c_sz, [c_i64]),
-    "ss_voxel_blur": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_p, c_sz, c_p]),
-    "ss_mask_max_samples": (c_i, []),
-    "ss_mask_key_bits": (c_i, []),
-    "ss_mask_keys": (c_i, [c_p, c_p, c_i, c_i64, c_f, c_p, c_p, c_p]),
-    "ss_mask_patches": (c_i, [c_p, c_p, c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_p]),
-    "ss_mask_select_blocks": (c_i, [c_i64]),
-    "ss_mask_select": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_mask_token_fwd": (c_i, [c_p, c_i, c_p, c_p, c_i64, c_i, c_p, c_p]),
-    "ss_mask_token_bwd_blocks": (c_i, [c_i64]),
-    "ss_mask_token_bwd_span": (c_i64, [c_i64]),
-    "ss_mask_token_bwd": (c_i, [c_p, c_i, c_p, c_i64, c_i, c_p, c_p, c_p, c_p]),
-    "ss_ema_group": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
-    "ss_knn_grid_table_size": (c_i64, [c_i64]),
-    "ss_knn_grid_workspace_bytes": (c_sz, [c_i64]),
-    "ss_knn_grid_keys": (c_i, [c_p, c_p, c_i, c_i64, c_f, c_f, c_f, c_f, c_p, c_p]),
-    "ss_knn_grid_build": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_sz, c_p, c_p]),
-    "ss_knn_grid_query": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i64, c_p, c_p, c_p, c_p]),
-    "ss_ball_grid_query": (c_i, [c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i64, c_p, c_p, c_p, c_p]),
-    "ss_knn_query": (c_i, [c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
-    "ss_ball_query_workspace_bytes": (c_sz, [c_i]),
-    "ss_ball_query": (c_i, [c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "ss_random_ball_query": (c_i, [c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
-    "ss_farthest_point_sampling": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_grouping_fwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
-    "ss_grouping_bwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
-    "ss_subtraction_fwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "ss_subtraction_bwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "ss_aggregation_fwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_aggregation_bwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_interpolation_fwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "ss_interpolation_bwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    "ss_attention_relation_fwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_attention_relation_bwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_attention_fusion_fwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_attention_fusion_bwd": (c_i, [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_rpe_dot_prod_fwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_rpe_dot_prod_bwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_rpe_attn_step2_fwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_rpe_attn_step2_bwd": (c_i, [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_majority_vote": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_i, c_p, c_p]),
-    "ss_vocab_finish_workspace_bytes": (c_sz, [c_i64, c_i, c_i64]),
-    "ss_vocab_finish": (c_i, [c_p, c_i64, c_i, c_i, c_f, ctypes.c_int32, c_p, c_i64, c_p, c_p, c_p, c_sz, c_p]),
-    "ss_cluster_vote_workspace_bytes": (c_sz, [c_i, c_i]),
-    "ss_cluster_vote": (c_i, [c_p, c_p, c_i64, c_i, c_i, ctypes.c_int32, c_p, c_p, c_sz, c_p]),
-    "ss_ballquery_batch_p": (c_i, [c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
-    "ss_bfs_cluster": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p]),
-}
+
+def _ctype(c_type, name):
+    if "*" in c_type:
+        return ctypes.c_void_p
+    c_type = " ".join(c_type.split())
+    if c_type not in _CTYPES:
+        raise ValueError(f"{name}: no ctypes type for the C type '{c_type}'")
+    return _CTYPES[c_type]
+
+
+def parse_header(text):
+    """C header text -> ({name: (restype, [argtypes])} of its ss_* declarations, {name: value} of its integer enums and #defines).
+    Strict: a type outside _CTYPES, or an ss_* name followed by `(` that did not parse as a declaration, raises (ctypes would pass
+    the arguments of a function without a prototype as C ints)."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    constants = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for item in body.split(","):
+            m = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item)
+            if not m:
+                raise ValueError(f"enum item '{item.strip()}' is not NAME = integer")
+            constants[m[1]] = int(m[2])
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    prototypes = {}
+    for ret, name, params in _DECL.findall(text):
+        params = [] if params.strip() == "void" else params.split(",")
+        # a parameter is a type and a name: the type is what stands in front of the last word
+        prototypes[name] = (_ctype(ret, name), [_ctype(re.sub(r"\w+\s*$", "", p), name) for p in params])
+    missed = set(re.findall(r"\b(ss_[a-z0-9_]+)\s*\(", text)) ^ set(prototypes)
+    if missed:
+        raise ValueError(f"not parsed as declarations: {sorted(missed)}")
+    return prototypes, constants
+
+
+with open(build.HEADER) as _f:
+    PROTOTYPES, CONSTANTS = parse_header(_f.read())
 
 _lib = None
 
@@ -216,7 +83,8 @@ class NativeError(RuntimeError):
     pass
 
 
-_STATUS = {1: "bad argument", 2: "kernel launch failed", 3: "workspace too small"}
+_STATUS = {CONSTANTS["SS_ERR_ARG"]: "bad argument", CONSTANTS["SS_ERR_LAUNCH"]: "kernel launch failed",
+           CONSTANTS["SS_ERR_WORKSPACE"]: "workspace too small"}
 
 
 def check(rc, name):

@@ -2,7 +2,6 @@
 // relative position encoding (ss_window_attn_rpe_*): one argument check, one SIMT / MFMA choice and one workspace layout,
 // dispatching to the SIMT kernels (attention_simt.hip) or the MFMA kernels (attention_mfma.hip, attention_rpe.hip).
 #include "attention_internal.h"
-#include "../../include/scenesplat_hip.h"
 
 extern "C" int ss_version(void) { return 101; }
 

@@ -22,7 +22,6 @@
 // Operand types, MFMA32, as_bf8 / cat_tr, max3 / swap32 and xcd_remap: attention_frag.h; the LDS-DMA wrappers and the plane
 // geometry (HMC / HMPlan) are this file's own.
 #include "attention_frag.h"
-#include "../../include/scenesplat_hip.h"
 #include <stdlib.h>
 
 #ifndef HM_THR

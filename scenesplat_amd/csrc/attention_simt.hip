@@ -18,7 +18,6 @@
 // with plain stores (summed in fixed order by k_rpe_dtable_reduce of attention_rpe.hip).  The RPE operands travel in a
 // trailing by-value struct that is empty for RPE = false, whose instantiations are the kernels without any of this.
 #include "attention_internal.h"
-#include "../../include/scenesplat_hip.h"
 #include <type_traits>
 
 #define AT_THREADS 256

@@ -13,7 +13,6 @@
 // fewer tiles than CUs, so the time is one tile's weight stream -- shared out over more waves with more loads in flight.
 #include "common.h"
 #include "rowmath.h"
-#include "../../include/scenesplat_hip.h"
 
 #define BT_R 32
 #define BT_MAX_BWD_BLOCKS 1024

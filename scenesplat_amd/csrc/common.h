@@ -3,14 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+#include "../../include/scenesplat_hip.h"   // the status codes, and every entry point's declaration for its definition to match
 
-#define SS_OK 0
-#define SS_ERR_ARG 1
-#define SS_ERR_LAUNCH 2
-#define SS_ERR_WORKSPACE 3
-
-#define SS_F32 0
-#define SS_BF16 1
+#define SS_F32 SS_DTYPE_F32
+#define SS_BF16 SS_DTYPE_BF16
 
 // Launch + immediate status check.  The sticky HIP error is cleared first: the host process
 // (PyTorch) may have left an unrelated non-fatal error (e.g. hipErrorNotReady from an event

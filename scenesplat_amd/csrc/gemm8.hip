@@ -30,7 +30,6 @@
 //     conflict-free is applied to the per-lane SOURCE chunk and again on the read.
 #include "common.h"
 #include <stdlib.h>
-#include "../../include/scenesplat_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 g8_bf8_t;
 #define G8_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)

@@ -10,7 +10,6 @@
 // (d sums, optional d p) into d f.  One wave per row, the row lives in registers (C % 4 == 0, C <= 2048); per-wave
 // partial sums -> LDS -> per-block partials -> a single-block finish kernel (deterministic, no atomics).
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 #define HD_THREADS 256
 #define HD_MAX_BLOCKS 1024

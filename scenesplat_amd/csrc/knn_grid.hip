@@ -19,7 +19,6 @@
 //           Rings beyond SS_KNN_RING_MAX fall back to a wave-wide scan of the batch element (sparse outliers), so the worst case per
 //           query is the brute-force cost spread over 64 lanes.
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 #define KG_THREADS 256
 #define KG_WAVES (KG_THREADS / 64)

@@ -10,7 +10,6 @@
 // coalesced 1 KiB / 512 B per wave instruction); the row lives in registers between the two passes.
 #include "grouped.h"
 #include "rowmath.h"
-#include "../../include/scenesplat_hip.h"
 
 #define LN_THREADS 256
 #define LN_MAXIT 4   // C <= 1024

@@ -7,7 +7,6 @@
 // Grouped launches (grouped.h), one descriptor row per tensor; a workgroup of 256 threads owns OPTG_PER_WG consecutive elements of
 // one tensor.  No atomics anywhere: every sum has a fixed order, so results are bitwise reproducible.
 #include "grouped.h"
-#include "../../include/scenesplat_hip.h"
 
 #define OPTG_PER_WG 8192
 #define OPTG_FLAG_VEC16 1        // every base pointer of the row is 16-byte aligned: 16-byte lanes; else one element per lane

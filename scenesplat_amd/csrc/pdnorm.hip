@@ -9,7 +9,6 @@
 // two rows of W that a channel needs (c: shift, C + c: scale) are read once, coalesced.  Sums have a fixed order (lane-strided,
 // xor butterfly, waves in order, workgroup partials in order): no atomics, results are bitwise reproducible.
 #include "grouped.h"
-#include "../../include/scenesplat_hip.h"
 
 #define PDN_WORDS 14          // int64 words per table row, see scenesplat_hip.h
 #define PDN_CH_PER_WG 16

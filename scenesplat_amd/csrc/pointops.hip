@@ -16,7 +16,6 @@
 #include <queue>
 #include <vector>
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 #define PO_THREADS 256
 #define PO_TILE 1024   // candidate points staged per LDS tile

@@ -4,7 +4,6 @@
 // torch_scatter.segment_csr (ptv3:416-421).  Every source row and index is read once and every
 // destination row written once, 16 bytes per lane where the row width allows.
 #include "grouped.h"
-#include "../../include/scenesplat_hip.h"
 
 template <typename V>
 __global__ void k_gather_rows(const V* __restrict__ src, const int32_t* __restrict__ idx, V* __restrict__ dst,

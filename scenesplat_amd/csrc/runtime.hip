@@ -1,6 +1,5 @@
 // Small runtime queries of the C-ABI that have no kernel behind them.
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 // Capture status of a HIP stream: 0 = not capturing, 1 = capturing, 2 = capture invalidated (an illegal call was made while the
 // stream captured: the capture can only be abandoned; ending it crashes inside the runtime on this stack).  < 0: the query failed.

@@ -4,7 +4,6 @@
 // pred[idx[i]] (fragment voting in the tester).  One pass over the features: bf16 MFMA GEMM with the
 // sigmoid / max / arg-max / scatter fused into the epilogue; C <= 256 classes sit in one N tile.
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf8_t;
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)

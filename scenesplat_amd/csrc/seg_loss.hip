@@ -18,7 +18,6 @@
 //   4. k_seg_loss_finish  one block: fixed-order sums -> [ce_sum, n_valid, lovasz_sum over present classes, n_present].
 // The backward (k_seg_loss_bwd) is one pass per row.  No float atomics anywhere: two runs give bitwise-equal results.
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 #define SL_THREADS 256
 #define SL_MAX_BLOCKS 1024

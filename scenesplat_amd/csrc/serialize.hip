@@ -8,7 +8,6 @@
 // All work is HBM/L2-bound integer arithmetic: coalesced 8/16-byte accesses, one thread per
 // point, LDS only for the per-tile digit ranking of the radix sort.
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 // ------------------------------------------------------------------------------------------
 // curve keys

@@ -8,7 +8,6 @@
 //   mask token       out = mask ? token : x, and its backward (dx, dtoken).
 //   grouped EMA      teacher = m * teacher + (1 - m) * student over a descriptor table, the layout of ss_adamw_group (csrc/optim.hip).
 #include "grouped.h"
-#include "../../include/scenesplat_hip.h"
 
 namespace {
 

@@ -14,7 +14,6 @@
 //       ds_read_b64_tr_b16 with the same k permutation on both sides.
 // MFMA: v_mfma_f32_16x16x32_bf16, 128x128 workgroup tile, 4 waves (2x2) of 64x64, BK = 64.
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf8_t;
@@ -491,10 +490,6 @@ static bool conv_wgrad_uses_pipe(int64_t n, int cin, int cout, int taps) {
   return mode != 0 && ss_wgrad8_ok(n, cin, cout, taps) && (mode == 1 || (cout >= 128 && cin >= 128));
 }
 extern "C" int ss_subm_conv_wgrad_uses_pipe(int64_t n, int cin, int cout, int taps) { return conv_wgrad_uses_pipe(n, cin, cout, taps) ? 1 : 0; }
-
-extern "C" int ss_subm_conv_wgrad_walk(const void* in, const void* dout, const int32_t* nbr, const int32_t* nbr_walk,
-                                       const int32_t* rowperm, const int32_t* blk_count, const int32_t* blk_list, float* dweight,
-                                       int64_t n, int cin, int cout, int taps, hipStream_t stream);
 
 extern "C" int ss_subm_conv_wgrad(const void* in, const void* dout, const int32_t* nbr, const int32_t* rowperm,
                                   const int32_t* blk_count, const int32_t* blk_list, float* dweight, int64_t n, int cin,

@@ -17,7 +17,6 @@
 // global read gives a lane four consecutive channels, which serve four MFMA steps when the k order is permuted identically on both
 // sides (step (q, e), lane half kk  <->  channel 8 q + 4 kk + e).
 #include "common.h"
-#include "../../include/scenesplat_hip.h"
 
 #define F32MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 #define SF_TG 32          // taps per group held in the wave's LDS table

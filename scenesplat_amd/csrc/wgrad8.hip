@@ -16,7 +16,6 @@
 // Pipeline, phases, staggered wave rows and hazard rules: exactly gemm8.hip's (see its header).
 // GATHER: the (site, neighbour) ids of up to W8_CHUNK K-tiles live in LDS; longer shares are walked chunk by chunk.
 #include "grouped.h"
-#include "../../include/scenesplat_hip.h"
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 w8_bf8_t;

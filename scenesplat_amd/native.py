@@ -11,10 +11,11 @@ import torch
 from . import _lib, grouped
 from ._lib import check
 
-F32, BF16 = 0, 1
-ATTN_SIMT, ATTN_MFMA = 0, 1
+_C = _lib.CONSTANTS      # the enums of the header
+F32, BF16 = _C["SS_DTYPE_F32"], _C["SS_DTYPE_BF16"]
+ATTN_SIMT, ATTN_MFMA = _C["SS_ATTN_SIMT"], _C["SS_ATTN_MFMA"]
 HAVE_MFMA_ATTN = True  # bf16 MFMA window attention (csrc/attention_mfma.hip)
-ORDER_IDS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
+ORDER_IDS = {name: _C["SS_ORDER_" + name.upper().replace("-", "_")] for name in ("z", "z-trans", "hilbert", "hilbert-trans")}
 
 
 def _p(t):
@@ -309,7 +310,7 @@ def subm_conv_wgrad(x, dout, nbr, rowperm, blocks, out=None, nbr_walk=None):
     if nbr_walk is not None:
         _req(nbr_walk, torch.int32, "nbr_walk", (taps, n))
     check(lib().ss_subm_conv_wgrad_walk(_p(x), _p(dout), _p(nbr), _p(nbr_walk), _p(rowperm), _p(cnt), _p(lst), _p(dw), n, cin, cout, taps,
-                                        _stream()), "ss_subm_conv_wgrad")
+                                        _stream()), "ss_subm_conv_wgrad_walk")
     return dw
 
 

@@ -29,6 +29,85 @@ def test_library_exports_every_declared_symbol():
     assert lib.ss_version() >= 100
 
 
+# ---- the ctypes prototypes and the constants are parsed from the header (scenesplat_amd._lib.parse_header) ----
+SYNTHETIC_HEADER = """
+/* a comment that names ss_in_comment(int a, double b); and must not count */
+#ifndef X_H
+#define X_H
+#define SS_LIMIT 8
+enum { SS_A = 0, SS_B = 1,
+       SS_C = -2 };
+int ss_three_lines(const void* a, int64_t n,
+                   float scale,
+                   ss_stream_t stream);
+int ss_none(void);
+int ss_out(int nwords, const uint32_t* mask, void** stream_out);
+int ss_bytes(const unsigned char* mask, const int* orders, uint64_t seed, int32_t ignore, size_t bytes);
+unsigned long long ss_id(ss_stream_t stream);
+size_t ss_size(int64_t n, int num);
+#endif
+"""
+
+
+def test_header_parser_on_synthetic_text():
+    from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_ulonglong, c_void_p
+    from scenesplat_amd._lib import parse_header
+    protos, consts = parse_header(SYNTHETIC_HEADER)
+    assert protos == {
+        "ss_three_lines": (c_int, [c_void_p, c_int64, c_float, c_void_p]),
+        "ss_none": (c_int, []),
+        "ss_out": (c_int, [c_int, c_void_p, c_void_p]),
+        "ss_bytes": (c_int, [c_void_p, c_void_p, c_uint64, c_int32, c_size_t]),
+        "ss_id": (c_ulonglong, [c_void_p]),
+        "ss_size": (c_size_t, [c_int64, c_int]),
+    }
+    assert consts == {"SS_LIMIT": 8, "SS_A": 0, "SS_B": 1, "SS_C": -2}
+
+
+@pytest.mark.parametrize("text", [
+    "int ss_bad(double x);",                                # a type outside the map
+    "int ss_bad(int a, short);",
+    "double ss_bad(int a);",
+    "int ss_good(void);\nint ss_bad(int a,\n",              # no closing `);`: the name census disagrees with the parsed set
+    "int ss_bad(int a,\nint ss_good(void);",
+])
+def test_header_parser_is_strict(text):
+    from scenesplat_amd._lib import parse_header
+    with pytest.raises(ValueError, match="ss_bad"):
+        parse_header(text)
+
+
+def test_prototypes_of_the_real_header():
+    from ctypes import c_float as f, c_int as i, c_int32, c_int64 as i64, c_size_t, c_uint64, c_ulonglong, c_void_p as p
+    from scenesplat_amd._lib import PROTOTYPES
+    assert len(PROTOTYPES) == len(header_symbols())
+    assert PROTOTYPES["ss_knn_grid_query"] == (i, [i, i, p, p, p, p, i, f, f, f, f, i, i, i, i64, p, p, p, p])
+    assert PROTOTYPES["ss_aug_gaussians"] == (i, [p, p, p, p, i64, p, p, i, p, p, i, f, f, p, c_uint64, p])
+    assert PROTOTYPES["ss_vocab_finish"] == (i, [p, i64, i, i, f, c_int32, p, i64, p, p, p, c_size_t, p])
+    assert PROTOTYPES["ss_stream_capture_id"] == (c_ulonglong, [p])
+    assert PROTOTYPES["ss_subm_rulebook_table_size"] == (i64, [i64])
+    assert PROTOTYPES["ss_argsort_workspace_bytes"] == (c_size_t, [i64, i])
+    assert PROTOTYPES["ss_block_tail_fwd"] == (i, [p, p, p, p, p, p, p, p, p, p, i, p, p, f, p, p, p, p, p, p, p, p, i64, i, p])
+    assert len(PROTOTYPES["ss_block_tail_fwd"][1]) == 25
+
+
+def test_loaded_functions_carry_the_parsed_prototypes(attn_lib):
+    from scenesplat_amd._lib import PROTOTYPES
+    for name, (res, args) in PROTOTYPES.items():
+        fn = getattr(attn_lib, name)
+        assert fn.restype == res and list(fn.argtypes) == args, name
+
+
+def test_constants_come_from_the_header():
+    from scenesplat_amd import _lib, native
+    expect = dict(SS_OK=0, SS_ERR_ARG=1, SS_ERR_LAUNCH=2, SS_ERR_WORKSPACE=3, SS_DTYPE_F32=0, SS_DTYPE_BF16=1, SS_ATTN_SIMT=0,
+                  SS_ATTN_MFMA=1, SS_ORDER_Z=0, SS_ORDER_Z_TRANS=1, SS_ORDER_HILBERT=2, SS_ORDER_HILBERT_TRANS=3, SS_MAX_ORDERS=8)
+    assert {k: _lib.CONSTANTS[k] for k in expect} == expect
+    assert _lib._STATUS == {1: "bad argument", 2: "kernel launch failed", 3: "workspace too small"}
+    assert (native.F32, native.BF16, native.ATTN_SIMT, native.ATTN_MFMA) == (0, 1, 0, 1)
+    assert native.ORDER_IDS == {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from scenesplat_amd import native as nv
