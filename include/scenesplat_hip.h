@@ -654,6 +654,53 @@ int ss_ballquery_batch_p(int n, int mean_active, float radius, const float* xyz,
 /* HOST pointers (CPU BFS, as the reference) */
 int ss_bfs_cluster(const int32_t* semantic_label, const int32_t* ball_query_idxs, const int32_t* start_len, int n, int threshold, int32_t* cluster_idxs, int64_t cap_points, int32_t* cluster_offsets, int64_t cap_clusters, int32_t* n_clusters, int32_t* n_points);
 
+/* ---- scene chunking (csrc/chunking.hip; pointcept/datasets/preprocessing/sampling_chunking_data_gs.py::chunking_scene) ----------
+ * The steps of chunking_scene over a scene arena on the device, values as numpy's bit for bit where the reference is deterministic.
+ * ss_chunk_extent: out6 = {min x, y, z, max x, y, z} of the rows x[idx[i]] (idx NULL: x[i]) of x (., 3) f32, i < m, m >= 1.
+ *   Deterministic: per-block partials (ss_chunk_extent_blocks(m) * 6 floats), then a finish step; no atomics.  NaN is skipped.
+ * ss_chunk_recentre: out[i][c] = coord[i][c] - ext6[c], one correctly rounded fp32 subtraction (ext6 is read on the device). */
+int ss_chunk_extent_blocks(int64_t m);
+int ss_chunk_extent(const float* x, const int32_t* idx, int64_t m, float* partials, float* out6, ss_stream_t stream);
+int ss_chunk_recentre(const float* coord, const float* ext6, int64_t n, float* out, ss_stream_t stream);
+/* lang_feat[valid == 1] /= norm(lang_feat[valid == 1], axis=1): rows (n, width) of dtype SS_CHUNK_F16 | SS_CHUNK_F32, in place; valid (n)
+ * bytes, a row is touched when its byte is non-zero.  One wave per row: fp32 sum of squares (lane l adds elements l, l + 64, ... in
+ * order, then a 6-level butterfly), correctly rounded sqrt and division, ONE rounding to the storage dtype.  A valid all-zero row
+ * becomes NaN, as in numpy. */
+enum { SS_CHUNK_F16 = 2, SS_CHUNK_F32 = 1 };
+int ss_chunk_lang_normalize(void* feat, int dtype, const uint8_t* valid, int64_t n, int width, ss_stream_t stream);
+/* Grid subsample.  ss_chunk_cell_keys: keys[i] = cx << (bits_y + bits_z) | cy << bits_z | cz with c = floor(x / grid_size), a correctly
+ * rounded fp32 division of the recentred coordinate.  bits_* >= 1; their sum above 63, or grid_size <= 0: SS_ERR_ARG.  status[0]
+ * (caller-zeroed int32) is set to 1 when a cell falls outside [0, 2^bits) of its axis (its key is then 0).
+ * ss_chunk_cell_pick: order / idx_ptr = the CSR that ss_pool_partition wrote over a stable argsort of the keys (cell c holds rows
+ *   order[idx_ptr[c] .. idx_ptr[c+1]), ascending).  first[c] = the cell's smallest row (int64: the key of the sort that puts the cells
+ *   in first-occurrence order); pick[c] = that row when valid is NULL or the cell has no valid row, else its valid row number
+ *   Philox4x32-10(key = seed; counter = {first[c] low, first[c] high, 0x43484e4b, 0}) word 0 mod n_valid, counted in ascending row order. */
+int ss_chunk_cell_keys(const float* rec, int64_t n, float grid_size, int bits_x, int bits_y, int bits_z, int64_t* keys,
+                       int32_t* status, ss_stream_t stream);
+int ss_chunk_cell_pick(const int32_t* order, const int32_t* idx_ptr, int64_t n_cells, const uint8_t* valid, uint64_t seed,
+                       int64_t* first, int32_t* pick, ss_stream_t stream);
+/* Chunk membership of the rows rec[pick[i]] (pick NULL: rec[i]), i < m, for ALL chunk origins at once.  bounds: fp64,
+ * {lo_x (nx), hi_x (nx), lo_y (ny), hi_y (ny)}, lo ascending, hi = lo + range: row i lies in chunk ix * ny + iy when
+ * lo_x[ix] <= x < hi_x[ix] and lo_y[iy] <= y < hi_y[iy], the fp32 coordinate converted to fp64 (numpy's promotion).
+ * slot_keys (m, slots): the row's chunks, in any order, and nx * ny in the unused slots; a stable
+ * sort of slot_keys lists every chunk's rows (sorted position / slots) in ascending row order, chunk after chunk.  slots >= the most
+ * chunks one row can lie in (ceil(range / stride) per axis, multiplied); a row in more chunks than that sets status[0] = 1 (caller-
+ * zeroed).  counts (nx * ny) int32, caller-zeroed: integer atomics (an LDS histogram per workgroup when nx * ny <= 2048). */
+int ss_chunk_membership(const float* rec, const int32_t* pick, int64_t m, const void* bounds, int nx, int ny, int slots,
+                        int64_t* slot_keys, int32_t* counts, int32_t* status, ss_stream_t stream);
+/* offsets (nchunk + 1) int64 = exclusive running sum of counts (one workgroup) */
+int ss_chunk_offsets(const int32_t* counts, int nchunk, int64_t* offsets, ss_stream_t stream);
+/* rows[p] = slot_order[p] / slots for the first `total` positions of the sorted slots (= offsets[nchunk]) */
+int ss_chunk_slot_rows(const int32_t* slot_order, int64_t total, int slots, int32_t* rows, ss_stream_t stream);
+/* Grouped row gather (a grouped launch, contract above): for every (chunk, asset) problem dst[i] = src[r], r = idx[i], or
+ * r = pick[idx[i]] when pick is given (the composition with a grid subsample: the subsampled scene is never materialised).
+ * desc: 8 words {src pointer, dst pointer, idx pointer (int32), n_rows, row_bytes < 2^31, pick pointer (int32) | 0, src_rows,
+ * pick_rows}; a row whose idx[i] lies outside [0, pick_rows) or whose r lies outside [0, src_rows) is not written.  Word size of the
+ * copy: 16 bytes when src, dst and row_bytes are multiples of 16, else 4, 2 or 1 by the same rule.  A workgroup owns
+ * ss_chunk_gather_rows_per_workgroup(row_bytes) rows; n_rows = 0 is legal. */
+int ss_chunk_gather_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
+int ss_chunk_gather_rows_per_workgroup(int64_t row_bytes);
+
 #ifdef __cplusplus
 }
 #endif

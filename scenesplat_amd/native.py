@@ -1628,3 +1628,117 @@ def ema_group(teacher, student, m, cache=None):
     tables = grouped.launch("ss_ema_group", desc, starts, dev, m, 1.0 - m)
     if cache is not None and not torch.cuda.is_current_stream_capturing():
         cache["key"], cache["launch"] = key, (tables, starts[-1])
+
+
+# ---- scene chunking (csrc/chunking.hip; the steps of sampling_chunking_data_gs.py::chunking_scene) ---------------------------------
+CHUNK_DTYPES = {torch.float16: _C["SS_CHUNK_F16"], torch.float32: _C["SS_CHUNK_F32"]}
+
+
+def chunk_extent(x, idx=None):
+    """(6,) f32 {min xyz, max xyz} of the rows x[idx] (idx int32; None: every row) of x (n, 3) f32; deterministic, NaN skipped."""
+    _rows3(x, "x")
+    if idx is not None:
+        _req(idx, torch.int32, "idx")
+    m = x.shape[0] if idx is None else idx.numel()
+    if m < 1:
+        raise ValueError("chunk_extent: no rows")
+    partials = torch.empty(lib().ss_chunk_extent_blocks(m) * 6, dtype=torch.float32, device=x.device)
+    out = torch.empty(6, dtype=torch.float32, device=x.device)
+    check(lib().ss_chunk_extent(_p(x), _p(idx), m, _p(partials), _p(out), _stream()), "ss_chunk_extent")
+    return out
+
+
+def chunk_recentre(coord, ext6):
+    """coord - ext6[:3] per column, one rounded fp32 subtraction (ext6 stays on the device)"""
+    _rows3(coord, "coord"); _req(ext6, torch.float32, "ext6", (6,))
+    out = torch.empty_like(coord)
+    check(lib().ss_chunk_recentre(_p(coord), _p(ext6), coord.shape[0], _p(out), _stream()), "ss_chunk_recentre")
+    return out
+
+
+def chunk_lang_normalize_(feat, valid):
+    """feat[valid != 0] /= its row norm, in place.  feat (n, width) fp16 | fp32; valid (n) uint8."""
+    _req(feat, None, "lang_feat")
+    if feat.dim() != 2 or feat.dtype not in CHUNK_DTYPES:
+        raise RuntimeError(f"lang_feat: expected (n, width) float16 | float32, got {tuple(feat.shape)} {feat.dtype}")
+    _req(valid, torch.uint8, "valid", (feat.shape[0],))
+    if feat.shape[1] < 1:
+        return feat
+    check(lib().ss_chunk_lang_normalize(_p(feat), CHUNK_DTYPES[feat.dtype], _p(valid), feat.shape[0], feat.shape[1], _stream()),
+          "ss_chunk_lang_normalize")
+    return feat
+
+
+def chunk_cell_keys(rec, grid_size, bits, status):
+    """int64 cell keys of floor(rec / grid_size) (fp32 IEEE division) packed with bits = (x, y, z) bits; status: (1,) int32, zeroed by
+    the caller, set when a cell does not fit.  More than 63 bits in all: NativeError."""
+    _rows3(rec, "rec"); _req(status, torch.int32, "status")
+    keys = torch.empty(rec.shape[0], dtype=torch.int64, device=rec.device)
+    check(lib().ss_chunk_cell_keys(_p(rec), rec.shape[0], float(grid_size), int(bits[0]), int(bits[1]), int(bits[2]), _p(keys), _p(status),
+                                   _stream()), "ss_chunk_cell_keys")
+    return keys
+
+
+def chunk_cell_pick(order, idx_ptr, n_cells, valid=None, seed=0):
+    """Per cell of the CSR (order, idx_ptr) over a stable argsort: (first (n_cells,) int64 = the smallest row, pick (n_cells,) int32 =
+    that row, or with `valid` (n) uint8 the cell's valid row number Philox(seed, first) mod n_valid when it has one)."""
+    _req(order, torch.int32, "order"); _req(idx_ptr, torch.int32, "idx_ptr")
+    if valid is not None:
+        _req(valid, torch.uint8, "valid", (order.numel(),))
+    if idx_ptr.numel() < n_cells + 1:
+        raise RuntimeError("idx_ptr shorter than n_cells + 1")
+    first = torch.empty(n_cells, dtype=torch.int64, device=order.device)
+    pick = torch.empty(n_cells, dtype=torch.int32, device=order.device)
+    check(lib().ss_chunk_cell_pick(_p(order), _p(idx_ptr), n_cells, _p(valid), int(seed) & (2 ** 64 - 1), _p(first), _p(pick), _stream()),
+          "ss_chunk_cell_pick")
+    return first, pick
+
+
+def chunk_membership(rec, pick, bounds, nx, ny, slots, status):
+    """Membership of the rows rec[pick] (pick None: every row) in the nx * ny chunks of `bounds` (fp64 {lo_x, hi_x, lo_y, hi_y}).
+    -> (slot_keys (m, slots) int64, counts (nx * ny) int32); status (1,) int32, caller-zeroed, set when a row needed more slots."""
+    _rows3(rec, "rec"); _req(bounds, torch.float64, "bounds", (2 * nx + 2 * ny,)); _req(status, torch.int32, "status")
+    if pick is not None:
+        _req(pick, torch.int32, "pick")
+    m = rec.shape[0] if pick is None else pick.numel()
+    if m * slots >= 2 ** 31:
+        raise RuntimeError(f"chunk_membership: {m} rows x {slots} slots do not fit the int32 sort order")
+    slot_keys = torch.empty((m, slots), dtype=torch.int64, device=rec.device)
+    counts = torch.zeros(nx * ny, dtype=torch.int32, device=rec.device)
+    check(lib().ss_chunk_membership(_p(rec), _p(pick), m, _p(bounds), int(nx), int(ny), int(slots), _p(slot_keys), _p(counts), _p(status),
+                                    _stream()), "ss_chunk_membership")
+    return slot_keys, counts
+
+
+def chunk_offsets(counts):
+    """(nchunk + 1,) int64 exclusive running sum of counts (nchunk,) int32"""
+    _req(counts, torch.int32, "counts")
+    offsets = torch.empty(counts.numel() + 1, dtype=torch.int64, device=counts.device)
+    check(lib().ss_chunk_offsets(_p(counts), counts.numel(), _p(offsets), _stream()), "ss_chunk_offsets")
+    return offsets
+
+
+def chunk_slot_rows(slot_order, total, slots):
+    """rows (total,) int32 = slot_order[:total] // slots"""
+    _req(slot_order, torch.int32, "slot_order")
+    if total > slot_order.numel():
+        raise RuntimeError("chunk_slot_rows: total exceeds the sorted slots")
+    rows = torch.empty(total, dtype=torch.int32, device=slot_order.device)
+    check(lib().ss_chunk_slot_rows(_p(slot_order), int(total), int(slots), _p(rows), _stream()), "ss_chunk_slot_rows")
+    return rows
+
+
+def chunk_gather_group(desc, dev):
+    """ONE launch of ss_chunk_gather_group over the rows of `desc` ((k, 8) int64: {src, dst, idx, n_rows, row_bytes, pick | 0, src_rows,
+    pick_rows}, real device addresses)."""
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    if desc.ndim != 2 or desc.shape[1] != 8:
+        raise RuntimeError("chunk_gather_group: desc must be (k, 8) int64")
+    if desc.shape[0] == 0:
+        return
+    if (desc[:, 3] < 0).any() or (desc[:, 4] < 1).any() or (desc[:, 4] >= 2 ** 31).any() or (desc[:, 6] < 0).any() or (desc[:, 7] < 0).any():
+        raise RuntimeError("chunk_gather_group: negative size, or row_bytes outside [1, 2^31)")
+    if ((desc[:, 3] > 0) & ((desc[:, 0] == 0) | (desc[:, 1] == 0) | (desc[:, 2] == 0))).any():
+        raise RuntimeError("chunk_gather_group: null pointer in a non-empty problem")
+    per = np.array([lib().ss_chunk_gather_rows_per_workgroup(int(rb)) for rb in desc[:, 4]], dtype=np.int64)
+    grouped.launch("ss_chunk_gather_group", desc, grouped.starts(_div_up(desc[:, 3], per)), dev)

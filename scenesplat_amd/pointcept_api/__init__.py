@@ -25,3 +25,13 @@ from . import datasets  # noqa: F401  (registers the dataset classes in DATASETS
 from .datasets import (DATASETS, ConcatDataset, DefaultDataset, DeviceLoader, GenericGSDataset, HoliCityGSDataset,  # noqa: F401
                        KITTI360GSDataset, Matterport3D_160_GSDataset, Matterport3DGSDataset, ScanNet200GSDataset, ScanNetGSDataset,
                        ScanNetPPGSDataset, build_dataset, build_test_loader, build_train_loader, build_val_loader)
+
+
+def __getattr__(name):
+    """preprocessing (scene chunking: writes the chunked splits the datasets read), chunk_scene, chunk_split: imported on first use,
+    so that `python -m scenesplat_amd.pointcept_api.preprocessing` finds the module not yet imported and runs it once."""
+    if name in ("preprocessing", "chunk_scene", "chunk_split"):
+        import importlib
+        module = importlib.import_module(".preprocessing", __name__)
+        return module if name == "preprocessing" else getattr(module, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
