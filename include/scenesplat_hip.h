@@ -701,6 +701,27 @@ int ss_chunk_slot_rows(const int32_t* slot_order, int64_t total, int slots, int3
 int ss_chunk_gather_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
 int ss_chunk_gather_rows_per_workgroup(int64_t row_bytes);
 
+/* ---- 3DGS checkpoint decode (csrc/ply.hip; scripts/preprocess_gs.py::read_gaussian_attributes, and read_gaussian_attribute of
+ * pointcept/datasets/preprocessing/holicity/preprocess_holicity_gs.py) -------------------------------------------------------------
+ * records: n whole vertex records of a binary little-endian .ply on the DEVICE, stride_bytes apart, 4-byte aligned.  h_offsets: a HOST
+ * table of 7 + n_scale + n_rot byte offsets inside a record, of the float32 properties x, y, z, f_dc_0..2, opacity,
+ * scale_0..n_scale-1, rot_0..n_rot-1; it travels as kernel arguments.  1 <= n_scale, n_rot <= 4.  The stride and every offset are
+ * multiples of 4 and offset + 4 <= stride; anything else: SS_ERR_ARG.  n == 0: SS_OK without a launch.
+ * Outputs, arrays of their own, contiguous:
+ *   coord (n, 3) f32     a copy
+ *   color (n, 3) u8      u8(clip(f32(f_dc * f32(0.28209479177387814)) + 0.5f, 0, 1) * 255): every operation rounded to fp32 on its
+ *                        own (no fma), the conversion truncates; NaN passes the clip
+ *   opacity (n) f32      1 / (1 + exp(-x)) in fp64, rounded once
+ *   scale (n, n_scale)   exp(x) in fp64, rounded once
+ *   quat (n, n_rot)      q / (sqrt(((q0^2 + q1^2) + q2^2) + q3^2) + f32(1e-9)) * sign(q0 of the quotient): fp32 steps in that order,
+ *                        IEEE square root and division; sign(0) = 0, so a record with rot_0 == 0 gives zeros (kept as the reference
+ *                        has it)
+ * A workgroup owns ss_ply_decode_rows_per_workgroup() consecutive records; a tile whose first byte is 16-byte aligned comes in with
+ * 16-byte loads, an 8-byte aligned one with 8-byte loads, any other with 4-byte loads. */
+int ss_ply_decode_rows_per_workgroup(void);
+int ss_ply_decode(const void* records, int64_t n, int stride_bytes, const int32_t* h_offsets, int n_scale, int n_rot, float* coord,
+                  uint8_t* color, float* opacity, float* scale, float* quat, ss_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

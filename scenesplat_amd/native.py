@@ -1742,3 +1742,32 @@ def chunk_gather_group(desc, dev):
         raise RuntimeError("chunk_gather_group: null pointer in a non-empty problem")
     per = np.array([lib().ss_chunk_gather_rows_per_workgroup(int(rb)) for rb in desc[:, 4]], dtype=np.int64)
     grouped.launch("ss_chunk_gather_group", desc, grouped.starts(_div_up(desc[:, 3], per)), dev)
+
+
+# ---- 3DGS checkpoint decode (csrc/ply.hip) ---------------------------------------------------------------------------------------------
+def ply_decode(records, n, stride, offsets, n_scale, n_rot, coord, color, opacity, scale, quat, row=0):
+    """ONE launch of ss_ply_decode: the first n records (stride bytes apart) of `records` (device uint8, 4-byte aligned) -> rows
+    row .. row + n of coord (N, 3) f32, color (N, 3) u8, opacity (N,) f32, scale (N, n_scale) f32, quat (N, n_rot) f32.  offsets: the
+    7 + n_scale + n_rot byte offsets of x, y, z, f_dc_0..2, opacity, scale_*, rot_* inside a record (host integers)."""
+    n, stride, row, n_scale, n_rot = int(n), int(stride), int(row), int(n_scale), int(n_rot)
+    _req(records, torch.uint8, "records")
+    offsets = [int(o) for o in offsets]
+    if not (1 <= n_scale <= 4 and 1 <= n_rot <= 4) or len(offsets) != 7 + n_scale + n_rot:
+        raise RuntimeError(f"ply_decode: n_scale / n_rot in 1..4 and 7 + n_scale + n_rot offsets expected, got {n_scale}, {n_rot}, {len(offsets)}")
+    if stride < 4 or stride % 4 or any(o < 0 or o % 4 or o + 4 > stride for o in offsets):
+        raise RuntimeError("ply_decode: the stride and every offset must be multiples of 4, and offset + 4 <= stride")
+    if n < 0 or row < 0 or records.numel() < n * stride or records.data_ptr() % 4:
+        raise RuntimeError("ply_decode: records must hold n whole records and start 4-byte aligned")
+    N = coord.shape[0] if isinstance(coord, torch.Tensor) and coord.dim() == 2 else -1
+    if row + n > N:
+        raise RuntimeError(f"ply_decode: rows {row}..{row + n} do not fit outputs of {N} rows")
+    _req(coord, torch.float32, "coord", (N, 3)); _req(color, torch.uint8, "color", (N, 3)); _req(opacity, torch.float32, "opacity", (N,))
+    _req(scale, torch.float32, "scale", (N, n_scale)); _req(quat, torch.float32, "quat", (N, n_rot))
+    if n == 0:
+        return
+
+    def at(t, width):
+        return ctypes.c_void_p(t.data_ptr() + row * width * t.element_size())
+
+    check(lib().ss_ply_decode(_p(records), n, stride, (ctypes.c_int32 * len(offsets))(*offsets), n_scale, n_rot, at(coord, 3), at(color, 3),
+                              at(opacity, 1), at(scale, n_scale), at(quat, n_rot), _stream()), "ss_ply_decode")

@@ -34,4 +34,9 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".preprocessing", __name__)
         return module if name == "preprocessing" else getattr(module, name)
+    # gaussian_ply (3DGS .ply checkpoints -> scene folders), likewise for `python -m scenesplat_amd.pointcept_api.gaussian_ply`
+    if name in ("gaussian_ply", "read_ply_header", "load_gaussian_ply", "transfer_labels", "preprocess_gs"):
+        import importlib
+        module = importlib.import_module(".gaussian_ply", __name__)
+        return module if name == "gaussian_ply" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
