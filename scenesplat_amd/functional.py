@@ -16,6 +16,11 @@ from torch.utils.weak import WeakIdKeyDictionary
 from . import native as nv
 
 
+def _bf16_autocast(x=None):
+    """Is CUDA bf16 autocast on (and x, when given, a GPU tensor): the condition of every bf16 fast path."""
+    return (x is None or x.is_cuda) and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+
+
 class _WindowAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, win, num_heads, scale, impl):
@@ -178,6 +183,34 @@ class _SubMConv3d(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+def _conv_meta(feat, weight, bias):
+    """What the MFMA conv backwards read beside their saved tensors: (in dtype, weight dtype, weight shape, cin, has bias)."""
+    return feat.dtype, weight.dtype, weight.shape, weight.shape[-1], bias is not None
+
+
+def _pad8(x, w):
+    """Zero-pad the channels of x (n, cin) and w (cout, taps, cin) to a multiple of 8 (the MFMA kernels' K step) -> (x, w, pad)."""
+    pad = (-x.shape[1]) % 8
+    if pad:
+        x = torch.nn.functional.pad(x, (0, pad)); w = torch.nn.functional.pad(w, (0, pad))
+    return x, w, pad
+
+
+def _dup_fold(dup_fn, nbr, g):
+    """Duplicate voxels (Mix3D batches): every site at a voxel reads the voxel's WINNER row, so the adjoint folds the gradients of all
+    duplicates onto their winner first (ss_dup_fold_rows); the other rows, which nobody reads, get zero gradient.  -> (runs, folded g)"""
+    runs = dup_fn() if dup_fn is not None else nv.dup_runs_from_rulebook(nbr)
+    return runs, nv.dup_fold_rows(g, runs)
+
+
+def _conv_blocks(blocks_fn, nbr, rowperm):
+    return blocks_fn() if blocks_fn is not None else nv.subm_block_lists(nbr, rowperm)     # (the level's cached wgrad block lists)
+
+
+def _bias_grad(g, w_dtype):
+    return g.sum(0, dtype=torch.float32).to(w_dtype)
+
+
 class _SubMConv3dFused(torch.autograd.Function):
     """bf16 MFMA implicit-GEMM path (csrc/subm_conv.hip): one launch each for forward, dgrad
     (same kernel, tap-mirrored transposed weights) and wgrad; duplicate voxels handled exactly."""
@@ -186,15 +219,10 @@ class _SubMConv3dFused(torch.autograd.Function):
     def forward(ctx, feat, weight, bias, nbr, rowperm, blocks_fn, has_dup, walk_fn=None, dup_fn=None):
         taps, n = nbr.shape
         cout, cin = weight.shape[0], weight.shape[-1]
-        pad = (-cin) % 8
-        ctx.dup_fn = dup_fn
-        x = feat.to(torch.bfloat16)
-        w = bf16_of(weight).reshape(cout, taps, cin)
-        if pad:
-            x = torch.nn.functional.pad(x, (0, pad)); w = torch.nn.functional.pad(w, (0, pad))
+        x, w, pad = _pad8(feat.to(torch.bfloat16), bf16_of(weight).reshape(cout, taps, cin))
         x, w = x.contiguous(), w.contiguous()
-        ctx.meta = (feat.dtype, weight.dtype, weight.shape, cin, bias is not None)
-        ctx.blocks_fn, ctx.has_dup = blocks_fn, has_dup
+        ctx.meta = _conv_meta(feat, weight, bias)
+        ctx.blocks_fn, ctx.has_dup, ctx.dup_fn = blocks_fn, has_dup, dup_fn
         ctx.wt = mirrored_of(weight) if not pad else None      # dgrad weight kept beside the shadow (functional.register_mirrored)
         ctx.im2col = n <= CONV_IM2COL_MAX_SITES
         # bf16 out under autocast (the next op is a bf16 GEMM); outside autocast (the evaluator's call form) the output
@@ -223,38 +251,24 @@ class _SubMConv3dFused(torch.autograd.Function):
         in_dtype, w_dtype, w_shape, cin, has_bias = ctx.meta
         g = dout.to(torch.bfloat16).contiguous()
         dx = dw = db = None
-        # duplicate voxels (Mix3D batches): every site at a voxel reads the voxel's WINNER row, so the adjoint first folds the
-        # gradients of all duplicates onto their winner (ss_dup_fold_rows), runs the symmetric gather on that, and leaves the
-        # non-winner rows (which nobody reads) with zero gradient
-        runs = gd = None
-        if ctx.has_dup and ctx.needs_input_grad[0]:
-            runs = ctx.dup_fn() if ctx.dup_fn is not None else nv.dup_runs_from_rulebook(nbr)
-            gd = nv.dup_fold_rows(g, runs)
-        if ctx.im2col:
-            cols = x                                               # saved im2col(x): (n, taps * cin_padded)
-            taps = nbr.shape[0]
-            if ctx.needs_input_grad[0]:
-                wt = ctx.wt if ctx.wt is not None else nv.subm_weight_mirror(w)   # [ci][t'][co] = w[co][T-1-t'][ci]
-                dx = torch.nn.functional.linear(nv.subm_im2col(g if gd is None else gd, nbr), wt.view(wt.shape[0], -1))
-                if runs is not None:
-                    nv.dup_zero_rows_(dx, runs)
-                dx = dx[:, :cin].to(in_dtype)
-            if ctx.needs_input_grad[1]:
-                dw = _mm_f32(g.t(), cols).view(w.shape)[:, :, :cin].reshape(w_shape).to(w_dtype)
-            if has_bias and ctx.needs_input_grad[2]:
-                db = g.sum(0, dtype=torch.float32).to(w_dtype)
-            return dx, dw, db, None, None, None, None, None, None
         if ctx.needs_input_grad[0]:
+            runs, gd = _dup_fold(ctx.dup_fn, nbr, g) if ctx.has_dup else (None, g)
             wt = ctx.wt if ctx.wt is not None else nv.subm_weight_mirror(w)       # [ci][t'][co] = w[co][T-1-t'][ci]
-            dx = nv.subm_conv_fwd(g if gd is None else gd, wt, None, nbr, rowperm, nbr_walk=walk)
+            if ctx.im2col:
+                dx = torch.nn.functional.linear(nv.subm_im2col(gd, nbr), wt.view(wt.shape[0], -1))
+            else:
+                dx = nv.subm_conv_fwd(gd, wt, None, nbr, rowperm, nbr_walk=walk)
             if runs is not None:
                 nv.dup_zero_rows_(dx, runs)
             dx = dx[:, :cin].to(in_dtype)
         if ctx.needs_input_grad[1]:
-            blocks = ctx.blocks_fn() if ctx.blocks_fn is not None else nv.subm_block_lists(nbr, rowperm)
-            dw = nv.subm_conv_wgrad(x, g, nbr, rowperm, blocks, nbr_walk=walk)[:, :, :cin].reshape(w_shape).to(w_dtype)
+            if ctx.im2col:                                         # x is the saved im2col(x): (n, taps * cin_padded)
+                dw = _mm_f32(g.t(), x).view(w.shape)
+            else:
+                dw = nv.subm_conv_wgrad(x, g, nbr, rowperm, _conv_blocks(ctx.blocks_fn, nbr, rowperm), nbr_walk=walk)
+            dw = dw[:, :, :cin].reshape(w_shape).to(w_dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            db = g.sum(0, dtype=torch.float32).to(w_dtype)
+            db = _bias_grad(g, w_dtype)
         return dx, dw, db, None, None, None, None, None, None
 
 
@@ -277,19 +291,15 @@ class _SubMConv3dSplit(torch.autograd.Function):
     def forward(ctx, feat, weight, bias, nbr, rowperm, blocks_fn, has_dup=False, dup_fn=None):
         taps, n = nbr.shape
         cout, cin = weight.shape[0], weight.shape[-1]
-        pad = (-cin) % 8
         ctx.has_dup, ctx.dup_fn = has_dup, dup_fn
-        x = feat.float()
-        w = weight.float().reshape(cout, taps, cin)
-        if pad:
-            x = torch.nn.functional.pad(x, (0, pad)); w = torch.nn.functional.pad(w, (0, pad))
+        x, w, _ = _pad8(feat.float(), weight.float().reshape(cout, taps, cin))
         xh, xl = _split_bf16(x)
         wh, wl = _split_bf16(w)
         x3 = torch.cat([xh, xl, xh], 1).contiguous()
         w3 = torch.cat([wh, wh, wl], 2).contiguous()
         out = nv.subm_conv_fwd(x3, w3, None if bias is None else bias.float().contiguous(), nbr, rowperm, torch.float32)
         ctx.save_for_backward(xh, xl, wh, wl, nbr, rowperm)
-        ctx.meta = (feat.dtype, weight.dtype, weight.shape, cin, bias is not None)
+        ctx.meta = _conv_meta(feat, weight, bias)
         ctx.blocks_fn = blocks_fn
         return out
 
@@ -304,21 +314,21 @@ class _SubMConv3dSplit(torch.autograd.Function):
             runs = None
             fh, fl = gh, gl
             if ctx.has_dup:      # duplicate voxels: fold the gradients of a voxel's sites onto its winner (fp32), then split
-                runs = ctx.dup_fn() if ctx.dup_fn is not None else nv.dup_runs_from_rulebook(nbr)
-                fh, fl = _split_bf16(nv.dup_fold_rows(dout.float().contiguous(), runs))
+                runs, folded = _dup_fold(ctx.dup_fn, nbr, dout.float().contiguous())
+                fh, fl = _split_bf16(folded)
             g3 = torch.cat([fh, fl, fh], 1).contiguous()
             dx = nv.subm_conv_fwd(g3, wt3, None, nbr, rowperm, torch.float32)
             if runs is not None:
                 nv.dup_zero_rows_(dx, runs)
             dx = dx[:, :cin].to(in_dtype)
         if ctx.needs_input_grad[1]:
-            blocks = ctx.blocks_fn() if ctx.blocks_fn is not None else nv.subm_block_lists(nbr, rowperm)
+            blocks = _conv_blocks(ctx.blocks_fn, nbr, rowperm)
             cp = xh.shape[1]
             d2 = nv.subm_conv_wgrad(torch.cat([xh, xl], 1).contiguous(), gh, nbr, rowperm, blocks)      # (cout, taps, 2 cp)
             d1 = nv.subm_conv_wgrad(xh, gl, nbr, rowperm, blocks)
             dw = (d2[:, :, :cp] + d2[:, :, cp:] + d1)[:, :, :cin].reshape(w_shape).to(w_dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            db = dout.sum(0, dtype=torch.float32).to(w_dtype)
+            db = _bias_grad(dout, w_dtype)
         return dx, dw, db, None, None, None, None, None
 
 
@@ -346,7 +356,7 @@ class _SubMConv3dF32(torch.autograd.Function):
         w = weight.float().reshape(cout, taps, cin)
         out = nv.subm_f32_fwd(x, nv.subm_f32_weight_layout(w), None if bias is None else bias.float().contiguous(), nbr, rowperm)
         ctx.save_for_backward(x, w, nbr, rowperm)
-        ctx.meta = (feat.dtype, weight.dtype, weight.shape, cin, bias is not None)
+        ctx.meta = _conv_meta(feat, weight, bias)
         ctx.blocks_fn = blocks_fn
         return out
 
@@ -357,17 +367,14 @@ class _SubMConv3dF32(torch.autograd.Function):
         g = dout.float().contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            if ctx.has_dup:
-                runs = ctx.dup_fn() if ctx.dup_fn is not None else nv.dup_runs_from_rulebook(ctx.plain_nbr)
-                dx = nv.subm_f32_fwd(nv.dup_fold_rows(g, runs), nv.subm_f32_weight_layout(w, mirror=True), None, nbr, rowperm,
-                                     winners_only=True).to(in_dtype)
-            else:
-                dx = nv.subm_f32_fwd(g, nv.subm_f32_weight_layout(w, mirror=True), None, nbr, rowperm).to(in_dtype)
+            gd = _dup_fold(ctx.dup_fn, ctx.plain_nbr, g)[1] if ctx.has_dup else g
+            dx = nv.subm_f32_fwd(gd, nv.subm_f32_weight_layout(w, mirror=True), None, nbr, rowperm,
+                                 winners_only=ctx.has_dup).to(in_dtype)
         if ctx.needs_input_grad[1]:
-            blocks = ctx.blocks_fn() if ctx.blocks_fn is not None else nv.subm_block_lists(ctx.orig_nbr, rowperm)
+            blocks = _conv_blocks(ctx.blocks_fn, ctx.orig_nbr, rowperm)
             dw = nv.subm_f32_wgrad(x, g, nbr, rowperm, blocks, cin).reshape(w_shape).to(w_dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            db = g.sum(0, dtype=torch.float32).to(w_dtype)
+            db = _bias_grad(g, w_dtype)
         return dx, dw, db, None, None, None, None, None, None
 
 
@@ -498,28 +505,51 @@ def lang_head_sums(pred, target, mask):
 # ---- bf16 shadows of fp32 parameters ------------------------------------------------------------------
 # torch autocast casts every fp32 weight / bias with its own ~4 us kernel (PT-v3m1: ~250 launches per step).  A model
 # can register its GEMM operands here and refresh ALL shadows with a few multi-tensor copies at the start of forward.
-# Every shadow carries the (version counter, storage address) of the parameter it was cast from: bf16_of() hands a
-# shadow out only while that stamp still matches, so a forward that nobody refreshed for (eval without autocast after
-# an optimizer step, load_state_dict, RUNTIME["param_shadows"] = False) gets a fresh cast instead of stale weights,
+# Every entry (_Copies: a shadow with its transposed / mirrored copies) carries the (version counter, storage address) of the parameter
+# it was written from: bf16_of() / bf16_t_of() / mirrored_of() hand a copy out only while that stamp still matches, so a forward that nobody
+# refreshed for (eval without autocast after an optimizer step, load_state_dict, param_shadows off) gets a fresh cast instead of stale weights,
 # and refresh_shadows() is a no-op while no parameter changed -- a second forward before the backward of the first
 # (LangPretrainer._chunked_forward in training, multi-view losses) does not overwrite tensors an autograd graph saved.
-_SHADOW = WeakIdKeyDictionary()          # parameter -> [bf16 tensor, stamp]; keyed by identity (Tensor.__eq__ is elementwise)
-_SHADOW_T = WeakIdKeyDictionary()        # parameter -> (in, out) bf16 copy (register_transposed)
-_SHADOW_M = WeakIdKeyDictionary()        # conv parameter -> tap-mirrored (cin, taps, cout) bf16 copy (register_mirrored)
+class _Copies:
+    """The bf16 copies of ONE parameter: the shadow, the optional (in, out) copy (register_transposed), the optional tap-mirrored
+    (cin, taps, cout) copy (register_mirrored), and the tag ALL of them were written under: _stamp(p) after an eager refresh,
+    ("capture", id) after one recorded inside a hipGraph capture, None while any of them has never been written."""
+    t = m = tag = None
+
+    def __init__(self, bf16):
+        self.bf16 = bf16
+
+    def set(self, which, copy):
+        """Allocate (a tensor) or drop (None) the "t" / "m" copy: THE place that invalidates the tag, until the next refresh."""
+        if getattr(self, which) is not copy:
+            setattr(self, which, copy)
+            self.tag = None
+
+    def want(self, which, shape, device):
+        """Keep a "t" / "m" copy of this shape (allocated unless it is there already)."""
+        have = getattr(self, which)
+        if have is None or have.shape != shape or have.device != device:
+            self.set(which, torch.empty(shape, dtype=torch.bfloat16, device=device))
+
+
+_SHADOW = WeakIdKeyDictionary()          # parameter -> _Copies; keyed by identity (Tensor.__eq__ is elementwise)
 
 
 def _stamp(p):
     return (p._version, p.data_ptr())
 
 
-def _shadow_current(ent, p):
-    """Is the shadow entry current: written eagerly for this parameter version, or recorded inside the capture now running."""
-    tag = ent[1]
-    if tag is None:
-        return False
-    if tag[0] == "capture":
-        return tag[1] != 0 and torch.cuda.is_current_stream_capturing() and tag[1] == nv.stream_capture_id()
-    return tag == _stamp(p)
+def _current(p):
+    """The entry of a registered parameter while its copies are current -- written eagerly for this parameter version, or recorded
+    inside the capture now running -- else None."""
+    ent = _SHADOW.get(p) if isinstance(p, torch.nn.Parameter) else None
+    if ent is None or ent.tag is None:
+        return None
+    if ent.tag[0] == "capture":
+        ok = ent.tag[1] != 0 and torch.cuda.is_current_stream_capturing() and ent.tag[1] == nv.stream_capture_id()
+    else:
+        ok = ent.tag == _stamp(p)
+    return ent if ok else None
 
 
 def register_shadows(params):
@@ -529,10 +559,9 @@ def register_shadows(params):
         if p is None or p.dtype != torch.float32 or not p.is_cuda:
             continue
         ent = _SHADOW.get(p)
-        if ent is None or ent[0].shape != p.shape or ent[0].device != p.device:
-            ent = [torch.empty_like(p, dtype=torch.bfloat16), None]
-            _SHADOW[p] = ent
-        src.append(p); dst.append(ent[0])
+        if ent is None or ent.bf16.shape != p.shape or ent.bf16.device != p.device:
+            ent = _SHADOW[p] = _Copies(torch.empty_like(p, dtype=torch.bfloat16))
+        src.append(p); dst.append(ent.bf16)
     return src, dst
 
 
@@ -541,43 +570,45 @@ SHADOW_GROUP_CAST = os.environ.get("SS_SHADOW_GROUP_CAST", "1") != "0"     # 0: 
 
 @torch.no_grad()
 def refresh_shadows(src, dst):
-    """Re-cast the parameters whose value changed since their shadow was written (all of them after an optimizer
-    step: one multi-tensor copy; none on a repeated forward)."""
-    todo_s, todo_d = [], []
+    """Re-cast the parameters whose value changed since their copies were written (all of them after an optimizer
+    step: one multi-tensor copy; none on a repeated forward), and with each shadow its (in, out) and tap-mirrored copies."""
     # inside a hipGraph capture every shadow is re-cast: the replayed step must pick up whatever the optimizer wrote
-    # since the previous replay, and a copy skipped now would be missing from the graph for good
-    everything = torch.cuda.is_current_stream_capturing()
-    cap = ("capture", nv.stream_capture_id()) if everything else None
+    # since the previous replay, and a copy skipped now would be missing from the graph for good.  There the copy is only
+    # RECORDED (it runs at replay): the entry is current for THIS capture only (_current compares the capture's identity)
+    # and stale for everything else, so that an eager step after a refused capture re-casts instead of trusting weights
+    # one optimizer step old
+    cap = ("capture", nv.stream_capture_id()) if torch.cuda.is_current_stream_capturing() else None
+    todo = []                                 # (parameter, shadow, its entry | None for a shadow that is no longer the registered one)
     for p, d in zip(src, dst):
         ent = _SHADOW.get(p)
-        st = _stamp(p)
-        if everything or ent is None or ent[0] is not d or ent[1] != st:
-            todo_s.append(p); todo_d.append(d)
-            if ent is not None and ent[0] is d:
-                # while capturing the copy is only RECORDED (it runs at replay): the shadow is current for THIS capture only
-                # (bf16_of / mirrored_of / transposed_of compare the capture's identity) and stale for everything else, so
-                # that an eager step after a refused capture re-casts instead of trusting weights one optimizer step old
-                ent[1] = cap if everything else st
-    if todo_s:
-        # one launch for all of them (torch._foreach_copy_ with a dtype change is one copy kernel PER TENSOR: 206 launches and
-        # 1.2 ms per step on the lang-pretrain model); anything that is not a contiguous fp32 -> bf16 pair takes the torch path
-        fast = [(s_, d_) for s_, d_ in zip(todo_s, todo_d) if s_.is_cuda and s_.dtype == torch.float32 and d_.dtype == torch.bfloat16
-                and s_.is_contiguous() and d_.is_contiguous() and s_.numel() == d_.numel()
-                and s_.data_ptr() % 16 == 0 and d_.data_ptr() % 16 == 0]      # (the group kernel moves 16-byte lanes from the tensor base)
-        if SHADOW_GROUP_CAST and fast:
-            nv.cast_bf16_group([a for a, _ in fast], [b for _, b in fast])
-            if len(fast) != len(todo_s):
-                done = {id(d_) for _, d_ in fast}
-                rest = [(s_, d_) for s_, d_ in zip(todo_s, todo_d) if id(d_) not in done]
-                torch._foreach_copy_([d_ for _, d_ in rest], [s_ for s_, _ in rest])
-        else:
-            torch._foreach_copy_(todo_d, todo_s)
-        pairs = [(d, _SHADOW_T[p]) for p, d in zip(todo_s, todo_d) if p in _SHADOW_T]
-        if pairs:
-            nv.transpose16_group(pairs)       # the (in, out) copies the dgrad GEMM reads, refreshed with their shadows
-        pairs = [(d.view(d.shape[0], -1, d.shape[-1]), _SHADOW_M[p]) for p, d in zip(todo_s, todo_d) if p in _SHADOW_M]
-        if pairs:
-            nv.subm_weight_mirror_group(pairs)   # the tap-mirrored (cin, taps, cout) copies the conv dgrad reads
+        if ent is not None and ent.bf16 is not d:
+            ent = None
+        tag = cap or _stamp(p)
+        if cap or ent is None or ent.tag != tag:
+            todo.append((p, d, ent))
+            if ent is not None:
+                ent.tag = tag
+    if not todo:
+        return
+    # one launch for all of them (torch._foreach_copy_ with a dtype change is one copy kernel PER TENSOR: 206 launches and
+    # 1.2 ms per step on the lang-pretrain model); anything that is not a contiguous fp32 -> bf16 pair takes the torch path
+    fast = [(s_, d_) for s_, d_, _ in todo if s_.is_cuda and s_.dtype == torch.float32 and d_.dtype == torch.bfloat16
+            and s_.is_contiguous() and d_.is_contiguous() and s_.numel() == d_.numel()
+            and s_.data_ptr() % 16 == 0 and d_.data_ptr() % 16 == 0]      # (the group kernel moves 16-byte lanes from the tensor base)
+    if SHADOW_GROUP_CAST and fast:
+        nv.cast_bf16_group([a for a, _ in fast], [b for _, b in fast])
+        if len(fast) != len(todo):
+            done = {id(d_) for _, d_ in fast}
+            rest = [(s_, d_) for s_, d_, _ in todo if id(d_) not in done]
+            torch._foreach_copy_([d_ for _, d_ in rest], [s_ for s_, _ in rest])
+    else:
+        torch._foreach_copy_([d_ for _, d_, _ in todo], [s_ for s_, _, _ in todo])
+    pairs = [(d, e.t) for _, d, e in todo if e is not None and e.t is not None]
+    if pairs:
+        nv.transpose16_group(pairs)           # the (in, out) copies the dgrad GEMM reads
+    pairs = [(d.view(d.shape[0], -1, d.shape[-1]), e.m) for _, d, e in todo if e is not None and e.m is not None]
+    if pairs:
+        nv.subm_weight_mirror_group(pairs)    # the tap-mirrored (cin, taps, cout) copies the conv dgrad reads
 
 
 def register_mirrored(weights):
@@ -586,25 +617,9 @@ def register_mirrored(weights):
     (cin % 8) and the split-precision convs build theirs on the fly as before."""
     for p in weights:
         ent = _SHADOW.get(p)
-        if ent is None or p.dim() != 5 or p.shape[-1] % 8:
-            continue
-        cout, cin = p.shape[0], p.shape[-1]
-        taps = p.numel() // (cout * cin)
-        m = _SHADOW_M.get(p)
-        if m is None or m.shape != (cin, taps, cout) or m.device != p.device:
-            _SHADOW_M[p] = torch.empty((cin, taps, cout), dtype=torch.bfloat16, device=p.device)
-            ent[1] = None
-
-
-def mirrored_of(p):
-    """The mirrored bf16 copy of a registered conv weight while its shadow is current, else None."""
-    if not isinstance(p, torch.nn.Parameter):
-        return None
-    m = _SHADOW_M.get(p)
-    if m is None:
-        return None
-    ent = _SHADOW.get(p)
-    return m if (ent is not None and _shadow_current(ent, p)) else None
+        if ent is not None and p.dim() == 5 and p.shape[-1] % 8 == 0:
+            cout, cin = p.shape[0], p.shape[-1]
+            ent.want("m", (cin, p.numel() // (cout * cin), cout), p.device)
 
 
 def register_transposed(weights):
@@ -613,42 +628,40 @@ def register_transposed(weights):
     register_shadows and before the refresh that follows it."""
     for p in weights:
         ent = _SHADOW.get(p)
-        if ent is None or p.dim() != 2:
-            continue
-        t = _SHADOW_T.get(p)
-        if t is None or t.shape != (p.shape[1], p.shape[0]) or t.device != p.device:
-            _SHADOW_T[p] = torch.empty((p.shape[1], p.shape[0]), dtype=torch.bfloat16, device=p.device)
-            ent[1] = None                     # force the next refresh to write both copies
+        if ent is not None and p.dim() == 2:
+            ent.want("t", (p.shape[1], p.shape[0]), p.device)
 
 
 def unregister_transposed(weights):
     """Drop the (in, out) copies of these weights: their layers run the NN form of the dgrad GEMM again."""
-    for p in weights:
-        if p in _SHADOW_T:
-            del _SHADOW_T[p]
+    for ent in filter(None, map(_SHADOW.get, weights)):
+        ent.set("t", None)
+
+
+def unregister_mirrored(weights):
+    """Drop the tap-mirrored copies of these conv weights: their dgrad builds its weight on the fly again."""
+    for ent in filter(None, map(_SHADOW.get, weights)):
+        ent.set("m", None)
+
+
+def mirrored_of(p):
+    """The mirrored bf16 copy of a registered conv weight while its entry is current, else None."""
+    ent = _current(p)
+    return ent.m if ent is not None else None
 
 
 def bf16_t_of(p):
-    """The transposed bf16 copy of a registered Linear weight while its shadow is current, else None."""
-    if not isinstance(p, torch.nn.Parameter):
-        return None
-    t = _SHADOW_T.get(p)
-    if t is None:
-        return None
-    ent = _SHADOW.get(p)
-    return t if (ent is not None and _shadow_current(ent, p)) else None
+    """The transposed bf16 copy of a registered Linear weight while its entry is current, else None."""
+    ent = _current(p)
+    return ent.t if ent is not None else None
 
 
 def bf16_of(p):
     """bf16 copy of an fp32 operand: the registered shadow while it is current, otherwise a fresh cast."""
-    if p is None:
-        return None
-    if p.dtype == torch.bfloat16:
+    if p is None or p.dtype == torch.bfloat16:
         return p
-    ent = _SHADOW.get(p) if isinstance(p, torch.nn.Parameter) else None
-    if ent is not None and _shadow_current(ent, p):
-        return ent[0]
-    return p.to(torch.bfloat16)
+    ent = _current(p)
+    return ent.bf16 if ent is not None else p.to(torch.bfloat16)
 
 
 # ---- grouped weight gradients of a stage ------------------------------------------------------------------------------
@@ -708,8 +721,7 @@ class _StageParams(torch.autograd.Function):
 def stage_begin(linears, n_rows):
     """Route the parameters of a stage's nn.Linear modules through one identity node (training under bf16 autocast only)."""
     _STAGE["cur"], _STAGE["route"] = None, {}
-    if not (WGRAD_GROUP_MAX_ROWS and LINEAR_WGRAD_MIN_ROWS <= n_rows <= WGRAD_GROUP_MAX_ROWS and torch.is_grad_enabled()
-            and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+    if not (WGRAD_GROUP_MAX_ROWS and LINEAR_WGRAD_MIN_ROWS <= n_rows <= WGRAD_GROUP_MAX_ROWS and torch.is_grad_enabled() and _bf16_autocast()):
         return
     params = [p for m in linears for p in (m.weight, m.bias) if p is not None and p.requires_grad and p.dtype == torch.float32 and p.is_cuda]
     # (the list holds the stage's nn.Linear AND nn.LayerNorm modules: both have .weight / .bias)
@@ -738,6 +750,14 @@ def _routed(p):
     return (a, _STAGE["cur"]) if a is not None else (p, None)
 
 
+def _linear_operands(weight, bias, cast_bias=True):
+    """What the Linear family hands its Function after x -> (weight, bias, w16, b16, stage, w16t): the parameters or, in a stage that
+    routes the weight, their aliases and that stage; the bf16 operands; the (in, out) copy for the NT dgrad form, if current."""
+    wr, stage = _routed(weight) if torch.is_grad_enabled() else (weight, None)
+    br = _routed(bias)[0] if stage is not None else bias
+    return wr, br, bf16_of(weight), bf16_of(bias) if cast_bias else None, stage, bf16_t_of(weight)
+
+
 class _Linear(torch.autograd.Function):
     """nn.Linear under bf16 autocast.  Forward and dgrad stay on hipBLASLt (NT / NN forms run at 0.9-1.3 PFLOP/s
     there); the weight gradient dy^T x -- K = sites, 0.25-0.7 PFLOP/s in hipBLASLt's TN form -- runs on the
@@ -747,19 +767,13 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, w16, b16, stage, w16t=None):
         y = torch.nn.functional.linear(x, w16, b16)
-        ctx.save_for_backward(x, w16 if w16t is None else w16t)
-        ctx.meta = (weight.dtype, bias is not None)
-        ctx.dgrad_nt = w16t is not None
-        ctx.stage = stage
+        _save_linear(ctx, x, weight, bias, w16, w16t, stage)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w16 = ctx.saved_tensors
-        w_dtype, has_bias = ctx.meta
-        dx, dw, db = _linear_backward(x, w16, ctx.dgrad_nt, w_dtype, has_bias, ctx.stage, dy.contiguous(), ctx.needs_input_grad[0],
-                                      ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        return dx, dw, db, None, None, None, None
+        return _linear_backward_of(ctx, x, w16, dy.contiguous()) + (None,) * 4
 
 
 class _LinearGelu(torch.autograd.Function):
@@ -771,23 +785,29 @@ class _LinearGelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, w16, b16, stage, w16t=None):
         u = torch.nn.functional.linear(x, w16, b16)
-        ctx.save_for_backward(x, w16 if w16t is None else w16t, u)
-        ctx.meta = (weight.dtype, bias is not None)
-        ctx.dgrad_nt = w16t is not None
-        ctx.stage = stage
+        _save_linear(ctx, x, weight, bias, w16, w16t, stage, u)
         return nv.gelu(u)
 
     @staticmethod
     def backward(ctx, dy):
         x, w16, u = ctx.saved_tensors
-        w_dtype, has_bias = ctx.meta
         dy = dy.contiguous()
         if not _aligned16(dy):
             dy = dy.clone()                     # a fresh allocation is 16-byte aligned (ss_gelu's lanes)
-        du = nv.gelu(u, dy)
-        dx, dw, db = _linear_backward(x, w16, ctx.dgrad_nt, w_dtype, has_bias, ctx.stage, du, ctx.needs_input_grad[0],
-                                      ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        return dx, dw, db, None, None, None, None
+        return _linear_backward_of(ctx, x, w16, nv.gelu(u, dy)) + (None,) * 4
+
+
+def _save_linear(ctx, x, weight, bias, w16, w16t, stage, *more):
+    """Keep on ctx what _linear_backward_of reads: x and the dgrad operand (the (in, out) copy when the layer registered one) in front
+    of the Function's own saved tensors, the parameter's dtype, whether there is a bias, and the stage that queues the weight gradient."""
+    ctx.save_for_backward(x, w16 if w16t is None else w16t, *more)
+    ctx.meta, ctx.dgrad_nt, ctx.stage = (weight.dtype, bias is not None), w16t is not None, stage
+
+
+def _linear_backward_of(ctx, x, w16, dy):
+    """(dx, dW, db) of the Linear that _save_linear recorded on ctx (x, w16: its first two saved tensors); inputs 0-2 are x, weight, bias."""
+    w_dtype, has_bias = ctx.meta
+    return _linear_backward(x, w16, ctx.dgrad_nt, w_dtype, has_bias, ctx.stage, dy, *ctx.needs_input_grad[:3])
 
 
 def _linear_backward(x, w16, dgrad_nt, w_dtype, has_bias, stage, dy, need_x, need_w, need_b):
@@ -824,29 +844,15 @@ LINEAR_WGRAD_MIN_ROWS = 1024     # in-process A/B on room-102400: 1024 beats 409
 
 def linear(x, weight, bias=None):
     """torch.nn.functional.linear; under CUDA bf16 autocast on 2-D input the backward uses the pipeline wgrad kernel."""
-    if x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16 \
-            and weight.dtype == torch.float32:
-        route = _STAGE["route"]
-        wr = route.get(id(weight)) if route else None
-        if wr is not None and torch.is_grad_enabled():
-            br = route.get(id(bias)) if bias is not None else None
-            return _Linear.apply(x.to(torch.bfloat16).contiguous(), wr, br if br is not None else bias, bf16_of(weight), bf16_of(bias),
-                                 _STAGE["cur"], bf16_t_of(weight))
-        return _Linear.apply(x.to(torch.bfloat16).contiguous(), weight, bias, bf16_of(weight), bf16_of(bias), None, bf16_t_of(weight))
+    if _bf16_autocast(x) and x.dim() == 2 and weight.dtype == torch.float32:
+        return _Linear.apply(x.to(torch.bfloat16).contiguous(), *_linear_operands(weight, bias))
     return torch.nn.functional.linear(x, weight, bias)
 
 
 def linear_gelu(x, weight, bias=None):
     """gelu(linear(x)) with the exact erf form; under CUDA bf16 autocast on 2-D input one autograd node (_LinearGelu)."""
-    if GELU_HIP and x.is_cuda and x.dim() == 2 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16 \
-            and weight.dtype == torch.float32 and torch.is_grad_enabled():
-        route = _STAGE["route"]
-        wr = route.get(id(weight)) if route else None
-        if wr is not None:
-            br = route.get(id(bias)) if bias is not None else None
-            return _LinearGelu.apply(x.to(torch.bfloat16).contiguous(), wr, br if br is not None else bias, bf16_of(weight), bf16_of(bias),
-                                     _STAGE["cur"], bf16_t_of(weight))
-        return _LinearGelu.apply(x.to(torch.bfloat16).contiguous(), weight, bias, bf16_of(weight), bf16_of(bias), None, bf16_t_of(weight))
+    if GELU_HIP and _bf16_autocast(x) and x.dim() == 2 and weight.dtype == torch.float32 and torch.is_grad_enabled():
+        return _LinearGelu.apply(x.to(torch.bfloat16).contiguous(), *_linear_operands(weight, bias))
     return gelu(linear(x, weight, bias))
 
 
@@ -868,20 +874,15 @@ class _QkvWindowAttentionHM(torch.autograd.Function):
                 qkv = qkv + b32.float()
             hm = nv.headmajor_pack(qkv.contiguous(), win, num_heads, 3, sec0)
         out, nlse2 = nv.window_attn_hm_fwd(hm, win, num_heads)
-        ctx.save_for_backward(x, w16 if w16t is None else w16t, hm, out, nlse2)
-        ctx.meta = (weight.dtype, bias is not None)
-        ctx.dgrad_nt = w16t is not None
-        ctx.stage, ctx.win, ctx.num_heads, ctx.scale = stage, win, num_heads, scale
+        _save_linear(ctx, x, weight, bias, w16, w16t, stage, hm, out, nlse2)
+        ctx.win, ctx.num_heads, ctx.scale = win, num_heads, scale
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, w16, hm, out, nlse2 = ctx.saved_tensors
-        w_dtype, has_bias = ctx.meta
         dqkv = nv.window_attn_hm_bwd(hm, out, dout.contiguous().to(torch.bfloat16), nlse2, ctx.win, ctx.num_heads, ctx.scale)
-        dx, dw, db = _linear_backward(x, w16, ctx.dgrad_nt, w_dtype, has_bias, ctx.stage, dqkv, ctx.needs_input_grad[0],
-                                      ctx.needs_input_grad[1], ctx.needs_input_grad[2])
-        return dx, dw, db, None, None, None, None, None, None
+        return _linear_backward_of(ctx, x, w16, dqkv) + (None,) * 6
 
 
 # below these: fp32 library GEMM + bias add + pack kernel (3 launches).  Round 4: 1,024 rows / 64 channels instead of 4,096 / 128 -- the
@@ -893,13 +894,9 @@ HM_FUSED_MIN_CHANNELS = int(os.environ.get("SS_HM_FUSED_MIN_CHANNELS", "64"))
 
 def qkv_window_attention(x, weight, bias, win, num_heads, scale):
     """SerializedAttention's qkv Linear + attention (ptv3:172-216) under CUDA bf16 autocast, MFMA path: (n, C) -> (n, C)."""
-    route = _STAGE["route"]
-    wr = route.get(id(weight)) if (route and torch.is_grad_enabled()) else None
-    br = route.get(id(bias)) if (wr is not None and bias is not None) else None
-    stage = _STAGE["cur"] if wr is not None else None
-    return _QkvWindowAttentionHM.apply(x.to(torch.bfloat16).contiguous(), wr if wr is not None else weight,
-                                       br if br is not None else bias, bf16_of(weight), stage, bf16_t_of(weight), win, num_heads,
-                                       scale)
+    x = x.to(torch.bfloat16).contiguous()
+    wr, br, w16, _, stage, w16t = _linear_operands(weight, bias, cast_bias=False)       # (the projection adds the fp32 bias itself)
+    return _QkvWindowAttentionHM.apply(x, wr, br, w16, stage, w16t, win, num_heads, scale)
 
 
 def window_attention_hm(qkv, win, num_heads, scale):
@@ -1170,11 +1167,7 @@ def block_tail_eligible(x, proj, ln2, fc1, fc2):
     for p in (proj.weight, proj.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, ln2.weight, ln2.bias):
         if not isinstance(p, torch.nn.Parameter) or p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
             return False
-    for w in (proj.weight, fc1.weight, fc2.weight):
-        ent = _SHADOW.get(w)
-        if ent is None or not _shadow_current(ent, w) or bf16_t_of(w) is None:
-            return False
-    return True
+    return all(bf16_t_of(w) is not None for w in (proj.weight, fc1.weight, fc2.weight))
 
 
 def block_tail(feat, x, rs1, rs2, proj, ln2, fc1, fc2, want_copy=False):

@@ -18,6 +18,7 @@ were trained with:
 """
 import os
 from functools import partial
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -153,8 +154,7 @@ class SerializedAttention(PointModule):
     def _forward_rpe(self, x, level, pre_proj=False):
         win = level.window(self.order_index, self.rpe_window_size(level))
         qkv = _lin(self.qkv, x)
-        bf16 = (x.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16) \
-            or qkv.dtype == torch.bfloat16
+        bf16 = SF._bf16_autocast(x) or qkv.dtype == torch.bfloat16
         if bf16 and (self.channels // self.num_heads) in (16, 32, 48, 64):
             impl = nv.ATTN_MFMA          # the library itself sends windows the MFMA kernels do not cover to the SIMT pair
         else:
@@ -170,9 +170,8 @@ class SerializedAttention(PointModule):
             return self._forward_rpe(x, level, pre_proj)
         win = level.window(self.order_index, self.patch_size)
         impl = RUNTIME["attn_impl"]
-        if (impl == nv.ATTN_MFMA and RUNTIME.get("attn_headmajor", True) and x.is_cuda and torch.is_autocast_enabled()
-                and torch.get_autocast_dtype("cuda") == torch.bfloat16 and self.qkv.weight.dtype == torch.float32
-                and (self.channels // self.num_heads) in (16, 32, 48, 64)):
+        if (impl == nv.ATTN_MFMA and RUNTIME.get("attn_headmajor", True) and SF._bf16_autocast(x)
+                and self.qkv.weight.dtype == torch.float32 and (self.channels // self.num_heads) in (16, 32, 48, 64)):
             # round 3: projection -> head-major, window-ordered q / k / v -> LDS-DMA attention kernels (csrc/attention_hm.hip)
             feat = SF.qkv_window_attention(x, self.qkv.weight, self.qkv.bias, win, self.num_heads, self.scale)
             return feat if pre_proj else _lin(self.proj, feat)
@@ -248,8 +247,7 @@ class Block(PointModule):
         """The fused Block tail (SF.block_tail) covers: bf16 autocast with the fused seams on, C in {32, 64, 128, 256} up to
         SF.BLOCK_TAIL_MAX_CHANNELS, hidden = 4C, exact-erf nn.GELU, plain fp32 nn.LayerNorm / nn.Linear parameters (a PDNorm-resolved
         LN2 takes the seam path) whose bf16 shadows and (in, out) copies are registered and current."""
-        if not (RUNTIME.get("fuse_block_tail", True) and RUNTIME.get("fuse_ln_seam", True) and x.is_cuda
-                and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+        if not (RUNTIME.get("fuse_block_tail", True) and RUNTIME.get("fuse_ln_seam", True) and SF._bf16_autocast(x)):
             return False
         mlp = self.mlp[0]
         if isinstance(self.norm2[0], PDNorm):
@@ -518,46 +516,52 @@ class PointTransformerV3(PointModule):
             cache[id(stage)] = ls
         return ls
 
+    def _copy_plan(self, key):
+        """Which parameters keep which bf16 copies, from the modules and the knobs in `key` (every knob read here is in it)."""
+        _, tail_max, fuse_tail, dgrad_nt, _, _ = key
+        plan = SimpleNamespace(key=key, params=[], wide=[])
+        # bf16 shadows: every Linear / SubMConv3d weight and bias (a conv's bias feeds the small levels' im2col GEMM as a bf16 operand)
+        skip = self._modulation_linears()
+        for m in self.modules():
+            if (isinstance(m, nn.Linear) and id(m) not in skip) or isinstance(m, SubMConv3d):
+                plan.params += [m.weight, m.bias]
+        # wide Linear layers of the two finest levels: an (in, out) copy for the NT form of their dgrad GEMM
+        stages = [getattr(self.enc, f"enc{s}", None) for s in (0, 1)] + [getattr(getattr(self, "dec", None), f"dec{s}", None) for s in (0, 1)]
+        for st in stages if dgrad_nt else ():
+            if st is not None:
+                plan.wide += [m.weight for m in st.modules() if isinstance(m, nn.Linear) and m.weight.numel() >= 65536]
+        # the fused Block tail reads the (in, out) copies of proj / fc1 / fc2 in its three dgrad products: for exactly the Blocks that
+        # can take it, so that every other Block keeps its own dgrad form
+        bound, have = (tail_max if fuse_tail else 0), {id(w) for w in plan.wide}
+        plan.tail = [w for m in self.modules() if isinstance(m, Block) and m.channels in SF.BLOCK_TAIL_CHANNELS and m.channels <= bound
+                     and m.pre_norm and not isinstance(m.norm2[0], PDNorm)
+                     and tuple(m.mlp[0].fc1.weight.shape) == (4 * m.channels, m.channels)
+                     for w in (m.attn.proj.weight, m.mlp[0].fc1.weight, m.mlp[0].fc2.weight) if id(w) not in have]
+        # dgrad weights of the convs that run on plain bf16 operands: mirrored once per refresh instead of once per backward call
+        plan.mirrored = [m.weight for m in self.modules() if isinstance(m, SubMConv3d) and conv_dtype_for(m.weight.shape[0]) == torch.bfloat16]
+        # fp32 accumulators of the weight / bias gradients: one zero-filled arena per step
+        plan.arena = sum(((p.numel() + 3) & ~3) for p in plan.params if p is not None) + 4 * len(plan.params)
+        return plan
+
     def _refresh_shadows(self):
-        """bf16 copies of every Linear / SubMConv3d weight and Linear bias, refreshed with multi-tensor copies."""
-        ps = self.__dict__.get("_shadow_lists")
-        # the fused Block tail's (in, out) copies are registered with the shadows, for exactly the Blocks that can take it: redone
-        # when the switch or the channel bound changes, so that every other Block keeps today's dgrad form
-        tail = SF.BLOCK_TAIL_MAX_CHANNELS if RUNTIME.get("fuse_block_tail", True) else 0
-        if ps is None or ps[2] != next(self.parameters()).device or ps[4] != tail:
-            params, skip = [], self._modulation_linears()
-            for m in self.modules():
-                if isinstance(m, nn.Linear) and id(m) not in skip:
-                    params += [m.weight, m.bias]
-                elif isinstance(m, SubMConv3d):
-                    params += [m.weight, m.bias]         # (the bias feeds the small levels' im2col GEMM as a bf16 operand)
-            src, dst = SF.register_shadows(params)
-            # wide Linear layers of the two finest levels: a transposed copy for the NT form of their dgrad GEMM
-            wide = []
-            for st in [getattr(self.enc, f"enc{s}", None) for s in (0, 1)] + [getattr(getattr(self, "dec", None), f"dec{s}", None) for s in (0, 1)]:
-                if st is not None:
-                    wide += [m.weight for m in st.modules() if isinstance(m, nn.Linear) and m.weight.numel() >= 65536]
-            if RUNTIME.get("dgrad_nt", True):
-                SF.register_transposed(wide)
-            # the fused Block tail reads the (in, out) copies of proj / fc1 / fc2 in its three dgrad products
-            keep = {id(w) for w in wide} if RUNTIME.get("dgrad_nt", True) else set()
-            mine = [w for m in self.modules() if isinstance(m, Block) and m.channels in SF.BLOCK_TAIL_CHANNELS and m.channels <= tail
-                    and m.pre_norm and not isinstance(m.norm2[0], PDNorm)
-                    and tuple(m.mlp[0].fc1.weight.shape) == (4 * m.channels, m.channels)
-                    for w in (m.attn.proj.weight, m.mlp[0].fc1.weight, m.mlp[0].fc2.weight) if id(w) not in keep]
-            SF.unregister_transposed([w for w in self.__dict__.get("_tail_transposed", []) if id(w) not in {id(v) for v in mine}])
-            SF.register_transposed(mine)
-            self.__dict__["_tail_transposed"] = mine
-            # dgrad weights of the convs that run on plain bf16 operands: mirrored once per refresh instead of once per backward call
-            SF.register_mirrored([m.weight for m in self.modules() if isinstance(m, SubMConv3d)
-                                  and conv_dtype_for(m.weight.shape[0]) == torch.bfloat16])
-            # fp32 accumulators of the weight / bias gradients: one zero-filled arena per step
-            total = sum(((p.numel() + 3) & ~3) for p in params if p is not None) + 4 * len(params)
-            ps = (src, dst, next(self.parameters()).device, total, tail)
-            self.__dict__["_shadow_lists"] = ps
-        SF.refresh_shadows(ps[0], ps[1])
+        """The bf16 copies of _copy_plan, refreshed with multi-tensor copies.  The plan is redone when a knob it reads changes and the
+        copies it no longer lists are dropped: the model holds what a freshly built one would."""
+        key = (next(self.parameters()).device, SF.BLOCK_TAIL_MAX_CHANNELS, bool(RUNTIME.get("fuse_block_tail", True)),
+               bool(RUNTIME.get("dgrad_nt", True)), RUNTIME["conv_dtype"], RUNTIME.get("conv_split_max_channels", 0))
+        plan = self.__dict__.get("_copies")
+        if plan is None or plan.key != key:
+            old, plan = plan, self._copy_plan(key)
+            plan.src, plan.dst = SF.register_shadows(plan.params)
+            if old is not None:
+                keep = {id(w) for w in plan.wide + plan.tail + plan.mirrored}
+                SF.unregister_transposed([w for w in old.wide + old.tail if id(w) not in keep])
+                SF.unregister_mirrored([w for w in old.mirrored if id(w) not in keep])
+            SF.register_transposed(plan.wide + plan.tail)
+            SF.register_mirrored(plan.mirrored)
+            self.__dict__["_copies"] = plan
+        SF.refresh_shadows(plan.src, plan.dst)
         if torch.is_grad_enabled():
-            nv.zero_arena_begin(ps[3], ps[2])
+            nv.zero_arena_begin(plan.arena, key[0])
 
     def _pdnorm(self):
         pds = self.__dict__.get("_pdnorm_list")
