@@ -701,6 +701,32 @@ int ss_chunk_slot_rows(const int32_t* slot_order, int64_t total, int slots, int3
 int ss_chunk_gather_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
 int ss_chunk_gather_rows_per_workgroup(int64_t row_bytes);
 
+/* ---- labelled point cloud of a batch of chunks (csrc/pc_attach.hip; pointcept/datasets/preprocessing/adding_pc_label_to_gs_chunk.py::
+ * SceneCache.slice and semseg_label_slice) ---------------------------------------------------------------------------------------------
+ * pc (M, 3) f32: the scene cloud.  q (m, 3) f32: the Gaussian centres of nc chunks, concatenated; chunk c owns the query rows
+ * q_offset[c] .. q_offset[c + 1] (q_offset (nc + 1) int32, ascending, q_offset[0] = 0).  idx (m, k) int32: the k nearest cloud rows of
+ * every query, nearest first, -1 in unfilled slots (ss_knn_query / ss_knn_grid_query).
+ * Limits (anything else: SS_ERR_ARG): 1 <= M < 2^31, nc >= 1, nc * ss_pc_bitmap_words(M) * 32 < 2^31, m * k < 2^31.
+ * ss_pc_mark: clears bitmap (nc, ss_pc_bitmap_words(M)) uint32 and status (1) itself, then per (query, j) pair: idx < 0 is skipped;
+ *   idx >= M sets status[0] = 1 and is never followed; else d = sqrt(dx * dx + dy * dy + dz * dz) in fp64 from the fp32 coordinates
+ *   (d? = (double)q? - (double)p?; every operation rounded on its own, the squares added in x, y, z order) and, where
+ *   d <= *h_dist_limit (a HOST double; it travels as a kernel argument), bit idx & 31 of bitmap[c][idx >> 5] is set with an integer
+ *   atomic OR (skipped when a plain load shows the bit set).  nearest[row] = idx[row][0] where its d <= limit, else -1.
+ *   The result does not depend on the order of arrival: two runs are byte-equal.
+ * ss_pc_compact_scan: popcounts per tile of 1,024 words (a chunk's tiles are consecutive; a partial last word counts no row >= M),
+ *   one exclusive scan over all tiles -> tile_base, and counts[c] (nc) int32 = the distinct rows of chunk c.  tile_base is a caller
+ *   buffer of 2 * ss_pc_compact_tiles(M, nc) + 1 int32 (the bases, then the per-tile counts).
+ * ss_pc_compact: rows[tile base + rank] = the cloud row of every set bit: the ascending rows of chunk 0, then of chunk 1, ...
+ *   (np.unique per chunk without a sort; chunk c's rows start at the running sum of counts).  capacity = the room of `rows`
+ *   (the sum of counts); nothing is written at or beyond it. */
+int64_t ss_pc_bitmap_words(int64_t M);
+int64_t ss_pc_compact_tiles(int64_t M, int nc);
+int ss_pc_mark(const float* pc, int64_t M, const float* q, int64_t m, const int32_t* q_offset, int nc, const int32_t* idx, int k,
+               const double* h_dist_limit, uint32_t* bitmap, int32_t* nearest, int32_t* status, ss_stream_t stream);
+int ss_pc_compact_scan(const uint32_t* bitmap, int64_t M, int nc, int32_t* tile_base, int32_t* counts, ss_stream_t stream);
+int ss_pc_compact(const uint32_t* bitmap, int64_t M, int nc, const int32_t* tile_base, int32_t* rows, int64_t capacity,
+                  ss_stream_t stream);
+
 /* ---- 3DGS checkpoint decode (csrc/ply.hip; scripts/preprocess_gs.py::read_gaussian_attributes, and read_gaussian_attribute of
  * pointcept/datasets/preprocessing/holicity/preprocess_holicity_gs.py) -------------------------------------------------------------
  * records: n whole vertex records of a binary little-endian .ply on the DEVICE, stride_bytes apart, 4-byte aligned.  h_offsets: a HOST

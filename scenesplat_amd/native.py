@@ -1771,3 +1771,41 @@ def ply_decode(records, n, stride, offsets, n_scale, n_rot, coord, color, opacit
 
     check(lib().ss_ply_decode(_p(records), n, stride, (ctypes.c_int32 * len(offsets))(*offsets), n_scale, n_rot, at(coord, 3), at(color, 3),
                               at(opacity, 1), at(scale, n_scale), at(quat, n_rot), _stream()), "ss_ply_decode")
+
+
+# ---- labelled point cloud of a batch of chunks (csrc/pc_attach.hip) ---------------------------------------------------------------------
+def pc_mark(pc, q, q_offset, idx, dist_limit):
+    """ss_pc_mark: pc (M, 3) f32, q (m, 3) f32, q_offset (nc + 1) int32, idx (m, k) int32 (-1 = unfilled), dist_limit: a Python float
+    (fp64).  -> (bitmap (nc, ceil(M / 32)) int32 words, nearest (m,) int32, status (1,) int32: 1 when an idx >= M was met)."""
+    _rows3(pc, "pc"); _rows3(q, "q"); _req(q_offset, torch.int32, "q_offset"); _req(idx, torch.int32, "idx")
+    M, m, nc = pc.shape[0], q.shape[0], q_offset.numel() - 1
+    if idx.dim() != 2 or idx.shape[0] != m or idx.shape[1] < 1:
+        raise RuntimeError(f"idx: expected (m = {m}, k >= 1), got {tuple(idx.shape)}")
+    if M < 1 or nc < 1:
+        raise RuntimeError("pc_mark: an empty cloud, or no chunk")
+    bitmap = torch.empty((nc, lib().ss_pc_bitmap_words(M)), dtype=torch.int32, device=pc.device)
+    nearest = torch.empty(m, dtype=torch.int32, device=pc.device)
+    status = torch.empty(1, dtype=torch.int32, device=pc.device)
+    limit = ctypes.c_double(float(dist_limit))
+    check(lib().ss_pc_mark(_p(pc), M, _p(q), m, _p(q_offset), nc, _p(idx), idx.shape[1], ctypes.addressof(limit), _p(bitmap), _p(nearest),
+                           _p(status), _stream()), "ss_pc_mark")
+    return bitmap, nearest, status
+
+
+def pc_compact_scan(bitmap, M):
+    """ss_pc_compact_scan -> (tile_base: the scan the emit pass reads, counts (nc,) int32: the distinct rows of every chunk)"""
+    _req(bitmap, torch.int32, "bitmap", (bitmap.shape[0], lib().ss_pc_bitmap_words(M)))
+    nc = bitmap.shape[0]
+    tile_base = torch.empty(2 * lib().ss_pc_compact_tiles(M, nc) + 1, dtype=torch.int32, device=bitmap.device)
+    counts = torch.empty(nc, dtype=torch.int32, device=bitmap.device)
+    check(lib().ss_pc_compact_scan(_p(bitmap), M, nc, _p(tile_base), _p(counts), _stream()), "ss_pc_compact_scan")
+    return tile_base, counts
+
+
+def pc_compact(bitmap, M, tile_base, total):
+    """ss_pc_compact -> rows (total,) int32: the ascending cloud rows of chunk 0, then of chunk 1, ...; total = counts.sum()"""
+    _req(bitmap, torch.int32, "bitmap", (bitmap.shape[0], lib().ss_pc_bitmap_words(M)))
+    _req(tile_base, torch.int32, "tile_base", (2 * lib().ss_pc_compact_tiles(M, bitmap.shape[0]) + 1,))
+    rows = torch.empty(int(total), dtype=torch.int32, device=bitmap.device)
+    check(lib().ss_pc_compact(_p(bitmap), M, bitmap.shape[0], _p(tile_base), _p(rows), int(total), _stream()), "ss_pc_compact")
+    return rows

@@ -39,4 +39,9 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".gaussian_ply", __name__)
         return module if name == "gaussian_ply" else getattr(module, name)
+    # pc_labels (the labelled point cloud of the original scene -> scene and chunk folders), likewise for its command line
+    if name in ("pc_labels", "slice_point_cloud", "attach_point_cloud"):
+        import importlib
+        module = importlib.import_module(".pc_labels", __name__)
+        return module if name == "pc_labels" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
