@@ -748,6 +748,41 @@ int ss_ply_decode_rows_per_workgroup(void);
 int ss_ply_decode(const void* records, int64_t n, int stride_bytes, const int32_t* h_offsets, int n_scale, int n_rot, float* coord,
                   uint8_t* color, float* opacity, float* scale, float* quat, ss_stream_t stream);
 
+/* ---- ScanNet mesh converter (csrc/mesh.hip; pointcept/datasets/preprocessing/scannet/preprocess_scannet.py and
+ * preprocess_scannet_gs.py: read_plymesh, vertex_normal, the label loop of handle_process) ---------------------------------------------
+ * ss_mesh_decode_vertices: n whole vertex records of a binary little-endian .ply on the DEVICE, stride_bytes apart, starting at ANY
+ * byte.  h_offsets: a HOST table of six byte offsets inside a record: the float32 properties x, y, z (multiples of 4, offset + 4 <=
+ * stride) and the uchar properties red, green, blue (anywhere).  -> coord (n, 3) f32 and color (n, 3) u8, copies.
+ * ss_mesh_decode_faces: n_faces records of 13 bytes (a uchar count, then three int32 or uint32 indices), starting at ANY byte ->
+ * faces (n_faces, 3) int32.  A count other than 3 ORs 1 into *status, an index outside [0, n_vertices) ORs 2; the caller zeroes
+ * status before the first piece and reads it once.  Both read the aligned 4-byte words that cover the records, so up to 3 bytes in
+ * front of `records` and behind the last record must belong to the same allocation.  A workgroup owns
+ * ss_mesh_decode_rows_per_workgroup() records; a caller that decodes in pieces hands in outputs advanced to the piece's first row. */
+enum { SS_MESH_FORM_PC = 0, SS_MESH_FORM_GS = 1 };
+int ss_mesh_decode_rows_per_workgroup(void);
+int ss_mesh_decode_vertices(const void* records, int64_t n, int stride_bytes, const int32_t* h_offsets, float* coord, uint8_t* color,
+                            ss_stream_t stream);
+int ss_mesh_decode_faces(const void* records, int64_t n_faces, int64_t n_vertices, int32_t* faces, int32_t* status, ss_stream_t stream);
+/* Vertex normals, bit-equal to the scripts' numpy: every fp32 operation rounded on its own, IEEE division and square root.
+ * ss_mesh_face_terms: terms (n_faces, 3) f32 = (vec / length) * area of every face, vec = cross(v1 - v0, v2 - v0) as mul, mul, sub,
+ * r = sqrt((x^2 + y^2) + z^2);  SS_MESH_FORM_PC: length = r + 1e-8f, area = length * 0.5f;  SS_MESH_FORM_GS: area = 0.5f * r,
+ * length = max(1e-8f, r).  An index outside [0, n_vertices) ORs 2 into *status and gives a zero term.
+ * ss_mesh_vertex_normals: order / idx_ptr / head / n_runs = what ss_argsort_i64 (stable) and ss_pool_partition wrote for the 3 *
+ * n_faces keys faces[face][corner] (entry p = 3 * face + corner).  One lane per run adds the terms of the run's faces in ascending
+ * face index into one fp32 accumulator per component (PC: a face once per vertex, GS: once per corner) and writes
+ * normal[v] = acc / length(sqrt((x^2 + y^2) + z^2)) with the form's length rule.  Rows of vertices in no face are NOT written: the
+ * caller zeroes normal (n_vertices, 3), which is their value in both forms.  No atomics. */
+int ss_mesh_face_terms(const float* coord, const int32_t* faces, int64_t n_faces, int64_t n_vertices, int form, float* terms,
+                       int32_t* status, ss_stream_t stream);
+int ss_mesh_vertex_normals(const float* terms, const int32_t* faces, const int32_t* order, const int32_t* idx_ptr, const int32_t* head,
+                           const int32_t* n_runs, int64_t n_faces, int64_t n_vertices, int form, float* normal, ss_stream_t stream);
+/* ss_mesh_labels: for row i < n: seg = seg_indices[src ? src[i] : i] (seg_indices: n_vertices int32), g = seg_to_group[seg]
+ * (n_segments int32, -1 = no group), outputs table20[g], table200[g], table_instance[g] (n_groups int32 each); -1 where the row, the
+ * segment or the group is out of range.  out_bytes 2: int16 outputs, 8: int64.  src: optional (n) int32 rows, or NULL. */
+int ss_mesh_labels(const int32_t* seg_indices, int64_t n_vertices, const int32_t* src, const int32_t* seg_to_group, int64_t n_segments,
+                   const int32_t* table20, const int32_t* table200, const int32_t* table_instance, int n_groups, int64_t n,
+                   int out_bytes, void* segment20, void* segment200, void* instance, ss_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

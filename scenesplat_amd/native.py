@@ -1773,6 +1773,118 @@ def ply_decode(records, n, stride, offsets, n_scale, n_rot, coord, color, opacit
                               at(opacity, 1), at(scale, n_scale), at(quat, n_rot), _stream()), "ss_ply_decode")
 
 
+# ---- ScanNet mesh converter (csrc/mesh.hip) ----------------------------------------------------------------------------------------------
+MESH_FORMS = {"pc": _C["SS_MESH_FORM_PC"], "gs": _C["SS_MESH_FORM_GS"]}
+MESH_FACE_BYTES = 13
+MESH_BAD_COUNT, MESH_BAD_INDEX = 1, 2        # the bits of the status word
+
+
+def _mesh_records(records, start, nbytes, name):
+    """address of byte `start` of `records` (device uint8); the kernels read the aligned words that cover [start, start + nbytes), which
+    torch's allocations (sized in multiples of 512 bytes, 256-byte aligned) always hold"""
+    _req(records, torch.uint8, "records")
+    if start < 0 or nbytes < 0 or start + nbytes > records.numel():
+        raise RuntimeError(f"{name}: bytes {start}..{start + nbytes} do not lie inside records of {records.numel()} bytes")
+    return ctypes.c_void_p(records.data_ptr() + start)
+
+
+def mesh_decode_vertices(records, n, stride, offsets, coord, color, row=0, start=0):
+    """ONE launch of ss_mesh_decode_vertices: n records, stride bytes apart, from byte `start` of `records` (device uint8; any alignment)
+    -> rows row .. row + n of coord (N, 3) f32 and color (N, 3) u8.  offsets: byte offsets of x, y, z (float32, multiples of 4) and of
+    red, green, blue (uchar) inside a record."""
+    n, stride, row, start = int(n), int(stride), int(row), int(start)
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != 6 or stride < 15 or any(o < 0 or o % 4 or o + 4 > stride for o in offsets[:3]) or any(not 0 <= o < stride for o in offsets[3:]):
+        raise RuntimeError("mesh_decode_vertices: six offsets inside the record expected, x / y / z at multiples of 4")
+    if n < 0 or row < 0:
+        raise RuntimeError("mesh_decode_vertices: negative count or row")
+    src = _mesh_records(records, start, n * stride, "mesh_decode_vertices")
+    N = coord.shape[0] if isinstance(coord, torch.Tensor) and coord.dim() == 2 else -1
+    if row + n > N:
+        raise RuntimeError(f"mesh_decode_vertices: rows {row}..{row + n} do not fit outputs of {N} rows")
+    _req(coord, torch.float32, "coord", (N, 3)); _req(color, torch.uint8, "color", (N, 3))
+    if n == 0:
+        return
+    check(lib().ss_mesh_decode_vertices(src, n, stride, (ctypes.c_int32 * 6)(*offsets), ctypes.c_void_p(coord.data_ptr() + row * 12),
+                                        ctypes.c_void_p(color.data_ptr() + row * 3), _stream()), "ss_mesh_decode_vertices")
+
+
+def mesh_decode_faces(records, n_faces, n_vertices, faces, status, row=0, start=0):
+    """ONE launch of ss_mesh_decode_faces: n_faces records of 13 bytes from byte `start` of `records` (device uint8; any alignment) ->
+    rows row .. row + n_faces of faces (F, 3) int32.  status (1,) int32, zeroed by the caller: mesh_check_status reads it."""
+    n_faces, n_vertices, row, start = int(n_faces), int(n_vertices), int(row), int(start)
+    if n_faces < 0 or row < 0 or not 0 <= n_vertices < 2 ** 31:
+        raise RuntimeError("mesh_decode_faces: negative count or row, or more than 2^31 - 1 vertices")
+    src = _mesh_records(records, start, n_faces * MESH_FACE_BYTES, "mesh_decode_faces")
+    F = faces.shape[0] if isinstance(faces, torch.Tensor) and faces.dim() == 2 else -1
+    if row + n_faces > F:
+        raise RuntimeError(f"mesh_decode_faces: rows {row}..{row + n_faces} do not fit faces of {F} rows")
+    _req(faces, torch.int32, "faces", (F, 3)); _req(status, torch.int32, "status", (1,))
+    if n_faces == 0:
+        return
+    check(lib().ss_mesh_decode_faces(src, n_faces, n_vertices, ctypes.c_void_p(faces.data_ptr() + row * 12), _p(status), _stream()),
+          "ss_mesh_decode_faces")
+
+
+def mesh_check_status(status, what):
+    """reads the status word once (a synchronisation); ValueError names what the kernels met"""
+    bits = int(status.item())
+    if bits & MESH_BAD_COUNT:
+        raise ValueError(f"{what}: a face with a vertex count other than 3 (only triangle meshes have a device form)")
+    if bits & MESH_BAD_INDEX:
+        raise ValueError(f"{what}: a face names a vertex outside [0, number of vertices)")
+
+
+def mesh_vertex_normals(coord, faces, form):
+    """coord (n, 3) f32, faces (F, 3) int32 -> normal (n, 3) f32, `vertex_normal` of preprocess_scannet.py (form 'pc') or
+    preprocess_scannet_gs.py (form 'gs') bit for bit: ss_mesh_face_terms, the stable argsort of the 3F corner entries by vertex,
+    ss_pool_partition's run boundaries, ss_mesh_vertex_normals.  ValueError: a face index outside [0, n)."""
+    if form not in MESH_FORMS:
+        raise ValueError(f"mesh_vertex_normals: form must be 'pc' or 'gs', got {form!r}")
+    n = coord.shape[0] if isinstance(coord, torch.Tensor) and coord.dim() == 2 else -1
+    F = faces.shape[0] if isinstance(faces, torch.Tensor) and faces.dim() == 2 else -1
+    _req(coord, torch.float32, "coord", (n, 3)); _req(faces, torch.int32, "faces", (F, 3))
+    if n >= 2 ** 31 or 3 * F >= 2 ** 31:
+        raise RuntimeError("mesh_vertex_normals: more than 2^31 - 1 vertices or corner entries")
+    dev = coord.device
+    normal = torch.zeros((n, 3), dtype=torch.float32, device=dev)          # a vertex in no face keeps 0 / length = 0
+    if F == 0:
+        return normal
+    if n == 0:
+        raise ValueError("mesh_vertex_normals: faces over an empty vertex list")
+    code = MESH_FORMS[form]
+    terms = torch.empty((F, 3), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().ss_mesh_face_terms(_p(coord), _p(faces), F, n, code, _p(terms), _p(status), _stream()), "ss_mesh_face_terms")
+    mesh_check_status(status, "mesh_vertex_normals")                       # (before the sort: its keys must be non-negative)
+    keys = faces.view(1, 3 * F).to(torch.int64)
+    order, _, _ = argsort_i64(keys, max(1, (n - 1).bit_length()), want_inverse=False, want_sorted=False)
+    _, idx_ptr, head, n_runs = pool_partition(keys.view(-1), order.view(-1), 0)
+    check(lib().ss_mesh_vertex_normals(_p(terms), _p(faces), _p(order), _p(idx_ptr), _p(head), _p(n_runs), F, n, code, _p(normal),
+                                       _stream()), "ss_mesh_vertex_normals")
+    return normal
+
+
+def mesh_labels(seg_indices, seg_to_group, table20, table200, table_instance, dtype, src=None):
+    """ONE launch of ss_mesh_labels -> (segment20, segment200, instance) of `dtype` (torch.int16 or torch.int64), one row per row of
+    `src` (int32 rows of seg_indices; None: one per entry of seg_indices).  Every table is int32 on the device."""
+    _req(seg_indices, torch.int32, "seg_indices"); _req(seg_to_group, torch.int32, "seg_to_group")
+    G = table20.numel() if isinstance(table20, torch.Tensor) else -1
+    for name, t in (("table20", table20), ("table200", table200), ("table_instance", table_instance)):
+        _req(t, torch.int32, name, (G,))
+    if dtype not in (torch.int16, torch.int64):
+        raise RuntimeError(f"mesh_labels: int16 or int64 outputs, got {dtype}")
+    if src is not None:
+        _req(src, torch.int32, "src")
+    n = seg_indices.numel() if src is None else src.numel()
+    outs = [torch.empty(n, dtype=dtype, device=seg_indices.device) for _ in range(3)]
+    if n:
+        check(lib().ss_mesh_labels(_p(seg_indices), seg_indices.numel(), _p(src), _p(seg_to_group), seg_to_group.numel(), _p(table20),
+                                   _p(table200), _p(table_instance), G, n, 2 if dtype == torch.int16 else 8, _p(outs[0]), _p(outs[1]),
+                                   _p(outs[2]), _stream()), "ss_mesh_labels")
+    return tuple(outs)
+
+
 # ---- labelled point cloud of a batch of chunks (csrc/pc_attach.hip) ---------------------------------------------------------------------
 def pc_mark(pc, q, q_offset, idx, dist_limit):
     """ss_pc_mark: pc (M, 3) f32, q (m, 3) f32, q_offset (nc + 1) int32, idx (m, k) int32 (-1 = unfilled), dist_limit: a Python float

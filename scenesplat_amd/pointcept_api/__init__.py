@@ -44,4 +44,10 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".pc_labels", __name__)
         return module if name == "pc_labels" else getattr(module, name)
+    # scannet_mesh (a raw ScanNet scan, and a checkpoint beside it -> the labelled scene folders), likewise for its command line
+    if name in ("scannet_mesh", "read_mesh_header", "load_ply_mesh", "mesh_vertex_normals", "scannet_label_tables", "group_tables",
+                "preprocess_scannet", "preprocess_scannet_gs"):
+        import importlib
+        module = importlib.import_module(".scannet_mesh", __name__)
+        return module if name == "scannet_mesh" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
