@@ -783,6 +783,35 @@ int ss_mesh_labels(const int32_t* seg_indices, int64_t n_vertices, const int32_t
                    const int32_t* table20, const int32_t* table200, const int32_t* table_instance, int n_groups, int64_t n,
                    int out_bytes, void* segment20, void* segment200, void* instance, ss_stream_t stream);
 
+/* ---- ScanNet++ converter (csrc/scannetpp.hip; pointcept/datasets/preprocessing/scannetpp/preprocess_scannetpp.py and
+ * preprocess_scannetpp_gs.py: Open3D's compute_vertex_normals(normalized=True) and the top-3 label loop of parse_scene) ---------------
+ * Vertex normals in Open3D's definition: fp64 throughout, every operation rounded on its own, IEEE division and square root.
+ * ss_mesh_face_cross_f64: cross (n_faces, 3) f64 = (v1 - v0) x (v2 - v0) of the fp32 coordinates widened to fp64, each component mul,
+ * mul, sub.  An index outside [0, n_vertices) ORs 2 into *status and gives a zero row.
+ * ss_mesh_vertex_normals_f64: order / idx_ptr / head / n_runs as for ss_mesh_vertex_normals.  One lane per run adds the cross products
+ * of the run's entries in ascending face index, once per corner, into three fp64 accumulators; z = (x^2 + y^2) + z^2; where z > 0 each
+ * component is divided by sqrt(z); the result is rounded once to fp32.  Rows of vertices in no face are NOT written: the caller zeroes
+ * normal (n_vertices, 3).  No atomics. */
+int ss_mesh_face_cross_f64(const float* coord, const int32_t* faces, int64_t n_faces, int64_t n_vertices, double* cross, int32_t* status,
+                           ss_stream_t stream);
+int ss_mesh_vertex_normals_f64(const double* cross, const int32_t* faces, const int32_t* order, const int32_t* idx_ptr,
+                               const int32_t* head, const int32_t* n_runs, int64_t n_faces, int64_t n_vertices, float* normal,
+                               ss_stream_t stream);
+/* The top-3 labels.  first3 (n_segments, 3) int32: per segment id the first three groups, in segGroups order, that carry a valid label
+ * and list the segment; -1 = an empty slot; slots fill from 0.  table_label / table_object (n_groups) int32.  The caller zeroes count
+ * (n_segments) and size (n_groups); the three run back to back on one stream, nothing is read on the host in between.
+ * ss_spp_segment_hist: count[s] += 1 for s = seg_indices[i] in [0, n_segments), i < n_vertices (at most 2^31 - 1).
+ * ss_spp_group_sizes: size[g] += count[s] for every slot g of first3[s] in [0, n_groups).  Integer atomics in both.
+ * ss_spp_labels: for row i < n: s = seg_indices[src ? src[i] : i], slots g_k = first3[s][k]; segment[i][k] = table_label[g_k],
+ * instance[i][k] = table_object[g_k], `empty` where the slot is empty.  With two or more used slots, p = the first slot of the smallest
+ * size[g_k], and columns 0 and p are swapped in both outputs.  A row or segment out of range, or a slot >= n_groups, gives `empty` in
+ * all three columns.  segment / instance: (n, 3) int16 at 4-byte aligned addresses, written a pair of rows (12 bytes) per lane. */
+int ss_spp_segment_hist(const int32_t* seg_indices, int64_t n_vertices, int64_t n_segments, int32_t* count, ss_stream_t stream);
+int ss_spp_group_sizes(const int32_t* first3, const int32_t* count, int64_t n_segments, int n_groups, int32_t* size, ss_stream_t stream);
+int ss_spp_labels(const int32_t* seg_indices, int64_t n_vertices, const int32_t* src, const int32_t* first3, int64_t n_segments,
+                  const int32_t* table_label, const int32_t* table_object, const int32_t* size, int n_groups, int64_t n, int empty,
+                  int16_t* segment, int16_t* instance, ss_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

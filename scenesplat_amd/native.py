@@ -1835,6 +1835,15 @@ def mesh_check_status(status, what):
         raise ValueError(f"{what}: a face names a vertex outside [0, number of vertices)")
 
 
+def _mesh_incidence(faces, n):
+    """the 3F corner entries faces[face][corner] (entry p = 3 * face + corner) under a stable argsort by vertex, with the run boundaries
+    of equal vertices: -> (order, idx_ptr, head, n_runs).  Every index must lie inside [0, n): the keys of the sort are non-negative."""
+    keys = faces.view(1, -1).to(torch.int64)
+    order, _, _ = argsort_i64(keys, max(1, (n - 1).bit_length()), want_inverse=False, want_sorted=False)
+    _, idx_ptr, head, n_runs = pool_partition(keys.view(-1), order.view(-1), 0)
+    return order, idx_ptr, head, n_runs
+
+
 def mesh_vertex_normals(coord, faces, form):
     """coord (n, 3) f32, faces (F, 3) int32 -> normal (n, 3) f32, `vertex_normal` of preprocess_scannet.py (form 'pc') or
     preprocess_scannet_gs.py (form 'gs') bit for bit: ss_mesh_face_terms, the stable argsort of the 3F corner entries by vertex,
@@ -1857,9 +1866,7 @@ def mesh_vertex_normals(coord, faces, form):
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     check(lib().ss_mesh_face_terms(_p(coord), _p(faces), F, n, code, _p(terms), _p(status), _stream()), "ss_mesh_face_terms")
     mesh_check_status(status, "mesh_vertex_normals")                       # (before the sort: its keys must be non-negative)
-    keys = faces.view(1, 3 * F).to(torch.int64)
-    order, _, _ = argsort_i64(keys, max(1, (n - 1).bit_length()), want_inverse=False, want_sorted=False)
-    _, idx_ptr, head, n_runs = pool_partition(keys.view(-1), order.view(-1), 0)
+    order, idx_ptr, head, n_runs = _mesh_incidence(faces, n)
     check(lib().ss_mesh_vertex_normals(_p(terms), _p(faces), _p(order), _p(idx_ptr), _p(head), _p(n_runs), F, n, code, _p(normal),
                                        _stream()), "ss_mesh_vertex_normals")
     return normal
@@ -1882,6 +1889,76 @@ def mesh_labels(seg_indices, seg_to_group, table20, table200, table_instance, dt
         check(lib().ss_mesh_labels(_p(seg_indices), seg_indices.numel(), _p(src), _p(seg_to_group), seg_to_group.numel(), _p(table20),
                                    _p(table200), _p(table_instance), G, n, 2 if dtype == torch.int16 else 8, _p(outs[0]), _p(outs[1]),
                                    _p(outs[2]), _stream()), "ss_mesh_labels")
+    return tuple(outs)
+
+
+# ---- ScanNet++ converter (csrc/scannetpp.hip) --------------------------------------------------------------------------------------------
+def mesh_vertex_normals_o3d(coord, faces):
+    """coord (n, 3) f32, faces (F, 3) int32 -> normal (n, 3) f32 in Open3D's definition (`compute_vertex_normals(normalized=True)`):
+    ss_mesh_face_cross_f64, the stable argsort of the 3F corner entries by vertex, ss_pool_partition's run boundaries,
+    ss_mesh_vertex_normals_f64.  ValueError: a face index outside [0, n)."""
+    n = coord.shape[0] if isinstance(coord, torch.Tensor) and coord.dim() == 2 else -1
+    F = faces.shape[0] if isinstance(faces, torch.Tensor) and faces.dim() == 2 else -1
+    _req(coord, torch.float32, "coord", (n, 3)); _req(faces, torch.int32, "faces", (F, 3))
+    if n >= 2 ** 31 or 3 * F >= 2 ** 31:
+        raise RuntimeError("mesh_vertex_normals_o3d: more than 2^31 - 1 vertices or corner entries")
+    dev = coord.device
+    normal = torch.zeros((n, 3), dtype=torch.float32, device=dev)          # a vertex in no face keeps its zero sum
+    if F == 0:
+        return normal
+    if n == 0:
+        raise ValueError("mesh_vertex_normals_o3d: faces over an empty vertex list")
+    cross = torch.empty((F, 3), dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().ss_mesh_face_cross_f64(_p(coord), _p(faces), F, n, _p(cross), _p(status), _stream()), "ss_mesh_face_cross_f64")
+    mesh_check_status(status, "mesh_vertex_normals_o3d")                   # (before the sort: its keys must be non-negative)
+    order, idx_ptr, head, n_runs = _mesh_incidence(faces, n)
+    check(lib().ss_mesh_vertex_normals_f64(_p(cross), _p(faces), _p(order), _p(idx_ptr), _p(head), _p(n_runs), F, n, _p(normal), _stream()),
+          "ss_mesh_vertex_normals_f64")
+    return normal
+
+
+def spp_segment_hist(seg_indices, n_segments):
+    """ONE launch of ss_spp_segment_hist: seg_indices (n,) int32 -> count (n_segments,) int32 of the ids inside [0, n_segments)"""
+    _req(seg_indices, torch.int32, "seg_indices")
+    n_segments = int(n_segments)
+    if seg_indices.dim() != 1 or seg_indices.numel() >= 2 ** 31 or n_segments < 0:
+        raise RuntimeError("spp_segment_hist: seg_indices must be (n,) with n < 2^31, n_segments >= 0")
+    count = torch.zeros(n_segments, dtype=torch.int32, device=seg_indices.device)
+    check(lib().ss_spp_segment_hist(_p(seg_indices), seg_indices.numel(), n_segments, _p(count), _stream()), "ss_spp_segment_hist")
+    return count
+
+
+def spp_group_sizes(first3, count, n_groups):
+    """ONE launch of ss_spp_group_sizes: first3 (S, 3) int32, count (S,) int32 -> size (n_groups,) int32"""
+    S = count.numel() if isinstance(count, torch.Tensor) else -1
+    _req(first3, torch.int32, "first3", (S, 3)); _req(count, torch.int32, "count", (S,))
+    n_groups = int(n_groups)
+    if not 0 <= n_groups < 2 ** 31:
+        raise RuntimeError("spp_group_sizes: n_groups outside [0, 2^31)")
+    size = torch.zeros(n_groups, dtype=torch.int32, device=count.device)
+    check(lib().ss_spp_group_sizes(_p(first3), _p(count), S, n_groups, _p(size), _stream()), "ss_spp_group_sizes")
+    return size
+
+
+def spp_labels(seg_indices, first3, table_label, table_object, size, src=None, empty=-1):
+    """ONE launch of ss_spp_labels -> (segment, instance) (n, 3) int16, one row per row of `src` (int32 rows of seg_indices; None: one
+    per entry of seg_indices).  Every table is int32 on the device; size = spp_group_sizes(...)."""
+    _req(seg_indices, torch.int32, "seg_indices")
+    S = first3.shape[0] if isinstance(first3, torch.Tensor) and first3.dim() == 2 else -1
+    _req(first3, torch.int32, "first3", (S, 3))
+    G = table_label.numel() if isinstance(table_label, torch.Tensor) else -1
+    for name, t in (("table_label", table_label), ("table_object", table_object), ("size", size)):
+        _req(t, torch.int32, name, (G,))
+    if src is not None:
+        _req(src, torch.int32, "src")
+    if not -2 ** 15 <= int(empty) < 2 ** 15:
+        raise RuntimeError(f"spp_labels: the empty value {empty} does not fit int16")
+    n = seg_indices.numel() if src is None else src.numel()
+    outs = [torch.empty((n, 3), dtype=torch.int16, device=seg_indices.device) for _ in range(2)]
+    if n:
+        check(lib().ss_spp_labels(_p(seg_indices), seg_indices.numel(), _p(src), _p(first3), S, _p(table_label), _p(table_object), _p(size), G,
+                                  n, int(empty), _p(outs[0]), _p(outs[1]), _stream()), "ss_spp_labels")
     return tuple(outs)
 
 

@@ -50,4 +50,10 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".scannet_mesh", __name__)
         return module if name == "scannet_mesh" else getattr(module, name)
+    # scannetpp_mesh (a raw ScanNet++ scan, and a checkpoint beside it -> the labelled scene folders), likewise for its command line
+    if name in ("scannetpp_mesh", "scannetpp_classes", "first_groups", "mesh_vertex_normals_o3d", "multilabels", "preprocess_scannetpp",
+                "preprocess_scannetpp_gs"):
+        import importlib
+        module = importlib.import_module(".scannetpp_mesh", __name__)
+        return module if name == "scannetpp_mesh" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
