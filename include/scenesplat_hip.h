@@ -281,6 +281,13 @@ int ss_linear_wgrad_group_plan(int64_t m, int k_in, int n_out, int64_t* desc_wor
 int ss_linear_wgrad_tiles(int k_in, int n_out);
 int ss_linear_wgrad_group_plan2(int64_t m, int k_in, int n_out, int launch_tiles, int64_t* desc_words);
 int ss_linear_wgrad_group(const int64_t* desc, const int32_t* wg_start, int nprob, int total_workgroups, ss_stream_t stream);
+/* The same group on a CAPPED grid of min(total_items, max_workgroups) persistent workgroups: workgroup b runs the items b, b + grid,
+ * b + 2 grid, ... (an item = what a workgroup is in ss_linear_wgrad_group).  A workgroup fills a CU, so a cap of CUs - R leaves R CUs
+ * to the kernels of another stream.  ..._plan_capped: the plan for such a launch -- K is split into up to four rounds of equally long
+ * items (never below 8 K-tiles of 64 rows per item), so that every workgroup gets the same number of items, give or take one. */
+int ss_linear_wgrad_group_plan_capped(int64_t m, int k_in, int n_out, int launch_tiles, int max_workgroups, int64_t* desc_words);
+int ss_linear_wgrad_group_capped(const int64_t* desc, const int32_t* wg_start, int nprob, int total_items, int max_workgroups,
+                                 ss_stream_t stream);
 /* small levels: split-K over tap ranges; acc32 (n,cout) f32 zeroed by the caller, receives out (+bias) */
 int ss_subm_conv_splits(int64_t n, int cout, int taps);
 int ss_subm_conv_fwd_splitk(const void* in, const void* weight, const float* bias, const int32_t* nbr, const int32_t* rowperm,

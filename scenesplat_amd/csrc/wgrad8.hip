@@ -368,6 +368,28 @@ k_wgrad8_group(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_
                  (float*)d[3], (int)m, k_in, n_out, 1, ntn, (int)((m + 63) / 64), min_per, ntiles, nshares, L);
 }
 
+// The same group on a CAPPED grid: gridDim.x = min(items, max_workgroups) persistent workgroups, workgroup b runs the items
+// b, b + grid, b + 2 grid, ...  An item is what a workgroup id is in k_wgrad8_group (problem, share, tile).  A workgroup holds 128 KiB of
+// the CU's 160 KiB of LDS, so two never share a CU: a grid of CUs - R leaves R CUs empty for whatever runs beside it.
+// w8_body in a loop: its early return only leaves the (inlined) body, i.e. skips the item; the accumulators are declared and zeroed
+// inside it; each wave has waited for its own LDS-DMA (vmcnt(0)) when it leaves the K loop, both wave rows have passed the same
+// number of barriers there, and the barrier below keeps a fast wave from re-staging LDS rows that a slow one still reads.
+__global__ void __launch_bounds__(512)
+k_wgrad8_group_capped(const int64_t* __restrict__ desc, const int32_t* __restrict__ wg_start, int nprob, int total_items) {
+  for (int b = blockIdx.x; b < total_items; b += (int)gridDim.x) {
+    const int p = group_owner(wg_start, nprob, b);
+    const int64_t* d = desc + (int64_t)p * 8;
+    const int64_t m = d[4];
+    const uint64_t w5 = (uint64_t)d[5], w6 = (uint64_t)d[6], w7 = (uint64_t)d[7];
+    const int k_in = (int)(w5 & 0xffffffffu), n_out = (int)(w5 >> 32);
+    const int ntn = (int)(w6 & 0xffffffffu), ntiles = (int)(w6 >> 32);
+    const int nshares = (int)(w7 & 0xffffffffu), min_per = (int)(w7 >> 32);
+    w8_body<false>((const unsigned short*)d[0], (const unsigned short*)d[1], nullptr, nullptr, nullptr, nullptr, (float*)d[2],
+                   (float*)d[3], (int)m, k_in, n_out, 1, ntn, (int)((m + 63) / 64), min_per, ntiles, nshares, b - wg_start[p]);
+    __syncthreads();
+  }
+}
+
 // XCD-aware tile order of the conv weight gradient: default OFF.  Stand-alone it wins (dec0 1.077 -> 1.041 ms, dec1 188 -> 184 us, two
 // repetitions), inside the step it loses (in-process interleaved A/B, scripts/ab_step.py wgrad_xcd: 37.48 ms with, 37.23 without).
 static int w8_xcd_flag = -1;
@@ -467,6 +489,43 @@ extern "C" int ss_linear_wgrad_group_plan2(int64_t m, int k_in, int n_out, int l
 }
 extern "C" int ss_linear_wgrad_group_plan(int64_t m, int k_in, int n_out, int64_t* desc_words) {
   return ss_linear_wgrad_group_plan2(m, k_in, n_out, 0, desc_words);
+}
+
+// Plan of one problem of a CAPPED launch (ss_linear_wgrad_group_capped on max_workgroups persistent workgroups).  One round of long
+// items would leave the workgroups that draw a second item a whole item behind (234 tiles on 224 workgroups: two rounds, the second
+// almost empty), so K is split further: every output tile gets floor(W8_CAP_ROUNDS * max_workgroups / launch_tiles) shares, i.e. the
+// launch is at most W8_CAP_ROUNDS full rounds of short items and the last, partial round costs one short item.  Shares stay at or above
+// the floor of 8 K-tiles (the 256-KiB atomic epilogue is paid per item), and a problem with fewer K-tiles is one share.
+#define W8_CAP_ROUNDS 4
+extern "C" int ss_linear_wgrad_group_plan_capped(int64_t m, int k_in, int n_out, int launch_tiles, int max_workgroups,
+                                                 int64_t* desc_words) {
+  if (m <= 0 || max_workgroups <= 0 || !ss_wgrad8_ok(m, k_in, n_out, 1) || !desc_words) return 0;
+  const int nblocks = ss_div_up(m, 64);
+  const int tm = ss_div_up(n_out, 256), tn = ss_div_up(k_in, 256);
+  const int64_t tiles_all = launch_tiles > tm * tn ? launch_tiles : tm * tn;
+  int64_t shares = (int64_t)W8_CAP_ROUNDS * max_workgroups / tiles_all;
+  if (shares < 1) shares = 1;
+  if (shares > nblocks / 8) shares = nblocks / 8 > 0 ? nblocks / 8 : 1;
+  // share s covers K-tiles [s * per, (s + 1) * per): take the largest share count whose LAST share is not below the floor either
+  int min_per = nblocks, splits = 1;
+  for (int s = (int)shares; s > 1; --s) {
+    const int per = ss_div_up(nblocks, s), n = ss_div_up(nblocks, per);
+    if (nblocks - (n - 1) * per >= 8) { min_per = per; splits = n; break; }
+  }
+  desc_words[5] = (int64_t)((uint64_t)(uint32_t)k_in | ((uint64_t)(uint32_t)n_out << 32));
+  desc_words[6] = (int64_t)((uint64_t)(uint32_t)tn | ((uint64_t)(uint32_t)(tm * tn) << 32));
+  desc_words[7] = (int64_t)((uint64_t)(uint32_t)splits | ((uint64_t)(uint32_t)min_per << 32));
+  return splits * tm * tn;
+}
+
+// desc as k_wgrad8_group reads it (planned by ss_linear_wgrad_group_plan_capped, or by ..._plan2); every dW / dbias zeroed.
+extern "C" int ss_linear_wgrad_group_capped(const int64_t* desc, const int32_t* wg_start, int nprob, int total_items,
+                                            int max_workgroups, hipStream_t stream) {
+  SS_GROUP_GUARD(desc, wg_start, nprob, total_items);
+  if (nprob > 128 || max_workgroups <= 0) return SS_ERR_ARG;
+  const int grid = total_items < max_workgroups ? total_items : max_workgroups;
+  SS_LAUNCH(k_wgrad8_group_capped, dim3((unsigned)grid), dim3(512), 0, stream, desc, wg_start, nprob, total_items);
+  return SS_OK;
 }
 
 // desc as k_wgrad8_group reads it; every dW / dbias zeroed.

@@ -684,11 +684,115 @@ _UNFLUSHED = set()       # stages that hold queued LayerNorm partial sums (see _
 WGRAD_GROUP_MAX_BYTES = int(float(os.environ.get("SS_WGRAD_GROUP_MAX_GIB", "8")) * (1 << 30))
 
 
+# ---- the weight gradients of the full-resolution decoder stages beside the coarse levels' backward --------------------------------
+# The grouped launch of dec0 takes every CU for 3 ms and feeds nothing downstream, while the backward of the pooled levels behind it
+# (dec2, enc3, enc2: 204 dependent launches in 2.7 ms, 175 of them shorter than 20 us) leaves most of the chip idle.  A stage of at least
+# WGRAD_DEFER_MIN_ROWS rows therefore does not launch at its flush: its queue moves to a deferred list, and when the backward leaves the
+# last consecutive such stage the list runs as ONE capped group (ss_linear_wgrad_group_capped) on a side stream, on CUs -
+# WGRAD_OVERLAP_FREE_CUS persistent workgroups -- a workgroup fills a CU, so that many CUs stay free for the chain.  While the group is in
+# flight the small stages HOLD their own grouped launches (128 KiB of LDS per workgroup: they would queue for the few free CUs); the
+# main stream joins the side stream in front of the next large stage, launches what was held, and in any case when the backward ends.
+# Gradient buffers are handed to autograd at the flush as always, zeroed, and filled later: nothing reads a .grad before the join.  That
+# needs autograd to keep the buffer itself as the parameter's .grad, so a stage whose parameters already have a .grad (gradient
+# accumulation) or gradient hooks launches at its flush as before.
+WGRAD_OVERLAP = os.environ.get("SS_WGRAD_OVERLAP", "1") != "0"
+WGRAD_DEFER_MIN_ROWS = int(os.environ.get("SS_WGRAD_DEFER_MIN_ROWS", "16384"))
+WGRAD_OVERLAP_FREE_CUS = int(os.environ.get("SS_WGRAD_OVERLAP_FREE_CUS", "80"))
+_OVERLAP = {"armed": False, "stages": [], "items": [], "pairs": [], "held": [], "flight": None, "callback": False, "streams": {}}
+OVERLAP_STATS = {"deferred": 0, "launched": 0, "joined": 0}      # stages deferred, capped launches, joins: call counters
+
+
+def wgrad_overlap_arm(on):
+    """Called by the model at the top of a forward: may this forward's backward defer weight gradients?  (The model says no for a
+    backward cut, whose caller takes dec0's gradients as final when the backward leaves dec0, and outside training.)"""
+    if _OVERLAP["flight"] is not None or _OVERLAP["items"] or _OVERLAP["held"]:
+        _overlap_clear()                          # left by a backward pass that died half way
+    _OVERLAP["armed"] = bool(on) and WGRAD_OVERLAP and WGRAD_DEFER_MIN_ROWS > 0
+    _OVERLAP["stages"] = []
+
+
+def _overlap_clear():
+    flight = _OVERLAP["flight"]
+    if flight is not None and not torch.cuda.is_current_stream_capturing():
+        flight[0].wait_stream(flight[1])          # the operands go back to the main stream's allocator
+    _OVERLAP.update(armed=False, stages=[], items=[], pairs=[], held=[], flight=None, callback=False)
+
+
+def _overlap_alias(stage, q):
+    """The queue with ALIASES of its accumulators, for a launch after the gradients have been handed to autograd: autograd keeps a
+    gradient that it owns alone as the parameter's .grad and copies one that somebody else still holds -- here: before it is filled."""
+    q = [(x, dy, dw.detach(), db.detach() if db is not None else None) for x, dy, dw, db in q]
+    stage.late = stage.late or {}
+    stage.late.update({t.data_ptr(): t for _, _, dw, db in q for t in (dw, db) if t is not None})
+    if not _OVERLAP["callback"]:
+        _OVERLAP["callback"] = True
+        torch.autograd.Variable._execution_engine.queue_callback(_overlap_finish)
+    return q
+
+
+def _overlap_launch():
+    """The deferred list as one capped group on the side stream, which first waits for everything the main stream holds so far."""
+    items, _OVERLAP["items"] = _OVERLAP["items"], []
+    main = torch.cuda.current_stream()
+    dev = items[0][0].device
+    side = _OVERLAP["streams"].get(dev)
+    if side is None:
+        side = _OVERLAP["streams"][dev] = torch.cuda.Stream(dev)
+    side.wait_stream(main)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    nv.linear_wgrad_group(items, max_workgroups=max(1, cus - WGRAD_OVERLAP_FREE_CUS), stream=side)
+    _OVERLAP["flight"] = (main, side, items)      # the operands were allocated on the main stream: kept until the join
+    OVERLAP_STATS["launched"] += 1
+
+
+def _overlap_join():
+    """The main stream waits for the side stream, then runs the grouped launches that the small stages held back."""
+    flight, _OVERLAP["flight"] = _OVERLAP["flight"], None
+    held, _OVERLAP["held"] = _OVERLAP["held"], []
+    if flight is None:
+        return None
+    main = flight[0]
+    with torch.cuda.stream(main):
+        main.wait_stream(flight[1])
+        for stage, q in held:
+            nv.linear_wgrad_group(q)
+            stage.late = None                     # (the stage that joins has not handed its gradients over yet: they are not late)
+    OVERLAP_STATS["joined"] += 1
+    return main
+
+
+def _overlap_finish():
+    """End of the backward pass (a callback of the autograd engine, on the stream backward() was called from, which the engine has
+    synchronised with the backward's streams by now): launch what was never launched, join, check the gradients."""
+    try:
+        cur = torch.cuda.current_stream()
+        if _OVERLAP["items"]:                     # the chain never left the deferring stages (no smaller stage behind them)
+            items, _OVERLAP["items"] = _OVERLAP["items"], []
+            nv.linear_wgrad_group(items)
+        main = _overlap_join() or cur
+        if cur != main:
+            cur.wait_stream(main)
+        # every late buffer must have become its parameter's .grad as it is: a copy would have been made before it was filled
+        for p, g in _OVERLAP["pairs"]:
+            if p.grad is None or p.grad.data_ptr() != g.data_ptr():
+                raise RuntimeError("a deferred weight gradient was copied before it was computed (a gradient hook?): "
+                                   "run with SS_WGRAD_OVERLAP=0")
+    finally:
+        _overlap_clear()
+
+
 class _WgradStage:
-    def __init__(self):
+    def __init__(self, n_rows=0, params=()):
         self.queue = []          # (x, dy, dW, db): nn.Linear weight gradients
         self.redq = []           # (part (K, nb, C), dst (K, C)): LayerNorm dgamma / dbeta partial sums
         self.bytes = 0
+        self.n_rows = n_rows
+        self.params = params     # what the stage's identity node routes, in its order
+        self.defer = False       # its queue runs beside the coarse levels' backward (see above)
+        self.prev = None         # the stage that the backward pass enters when it leaves this one
+        self.late = None         # data_ptr -> alias of the accumulators that are filled after this stage's flush
+        self.flushed = False
+        self.hooked = True       # its parameters may carry gradient hooks (until _overlap_enter has looked)
 
     def add(self, x, dy, dw, db):
         self.queue.append((x, dy, dw, db))
@@ -701,7 +805,23 @@ class _WgradStage:
         _UNFLUSHED.discard(self)
         q, self.queue, self.bytes = self.queue, [], 0
         r, self.redq = self.redq, []
-        nv.linear_wgrad_group(q)
+        first, self.flushed = not self.flushed, True
+        flight = _OVERLAP["flight"] is not None
+        # a launch after the hand-over needs autograd to KEEP the buffers it is handed: it accumulates into a .grad that exists (and
+        # copies under create_graph), reading them at once
+        late_ok = (q and (self.defer or flight) and not self.hooked and not torch.is_grad_enabled()
+                   and all(p.grad is None for p in self.params))
+        if late_ok and self.defer and not flight:
+            _OVERLAP["items"] += _overlap_alias(self, q)
+            OVERLAP_STATS["deferred"] += 1
+            if self.prev is None or not self.prev.defer:
+                _overlap_launch()
+        elif late_ok:
+            _OVERLAP["held"].append((self, _overlap_alias(self, q)))
+        else:
+            nv.linear_wgrad_group(q)
+        if flight and first and (self.prev is None or max(self.n_rows, self.prev.n_rows) >= WGRAD_DEFER_MIN_ROWS):
+            _overlap_join()                       # the next stage is a large one again (or this one is: the join is overdue)
         nv.group_partial_sums(r)
 
 
@@ -714,20 +834,43 @@ class _StageParams(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        ctx.stage.flush()
+        stage = ctx.stage
+        stage.flush()
+        ptrs, stage.late = stage.late, None
+        if ptrs:
+            _OVERLAP["pairs"] += [(p, ptrs[g.data_ptr()]) for p, g in zip(stage.params, grads) if g is not None and g.data_ptr() in ptrs]
         return (None,) + grads
+
+
+def _overlap_enter(stage, hooked):
+    """Place a stage in the order of this forward's stages and decide whether it defers (stage.params empty: a stage without a group,
+    which only takes its place in the order)."""
+    stages = _OVERLAP["stages"]
+    # only a stage with a small stage somewhere behind it in the backward pass (in front of it in the forward pass) defers: the
+    # decoder's full-resolution stages, not the encoder's
+    stage.defer = (bool(stage.params) and stage.n_rows >= WGRAD_DEFER_MIN_ROWS and not hooked
+                   and any(st.n_rows < WGRAD_DEFER_MIN_ROWS for st in stages))
+    stage.hooked = hooked
+    stage.prev = stages[-1] if stages else None
+    stages.append(stage)
 
 
 def stage_begin(linears, n_rows):
     """Route the parameters of a stage's nn.Linear modules through one identity node (training under bf16 autocast only)."""
     _STAGE["cur"], _STAGE["route"] = None, {}
-    if not (WGRAD_GROUP_MAX_ROWS and LINEAR_WGRAD_MIN_ROWS <= n_rows <= WGRAD_GROUP_MAX_ROWS and torch.is_grad_enabled() and _bf16_autocast()):
-        return
-    params = [p for m in linears for p in (m.weight, m.bias) if p is not None and p.requires_grad and p.dtype == torch.float32 and p.is_cuda]
-    # (the list holds the stage's nn.Linear AND nn.LayerNorm modules: both have .weight / .bias)
+    params = []
+    if WGRAD_GROUP_MAX_ROWS and LINEAR_WGRAD_MIN_ROWS <= n_rows <= WGRAD_GROUP_MAX_ROWS and torch.is_grad_enabled() and _bf16_autocast():
+        params = [p for m in linears for p in (m.weight, m.bias) if p is not None and p.requires_grad and p.dtype == torch.float32 and p.is_cuda]
+        # (the list holds the stage's nn.Linear AND nn.LayerNorm modules: both have .weight / .bias)
     if not params:
+        if _OVERLAP["armed"]:
+            _overlap_enter(_WgradStage(n_rows), False)
         return
-    stage = _WgradStage()
+    stage = _WgradStage(n_rows, params)
+    if _OVERLAP["armed"]:
+        # gradient hooks (the stage-wise gradient exchange, DistributedDataParallel) read a gradient when autograd hands it over
+        _overlap_enter(stage, any(getattr(p, "_post_accumulate_grad_hooks", None) or p._backward_hooks for p in params) or (
+            torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1))
     aliases = _StageParams.apply(stage, *params)
     _STAGE["cur"], _STAGE["route"] = stage, {id(p): a for p, a in zip(params, aliases)}
 
@@ -737,11 +880,12 @@ def stage_end():
 
 
 def reset_state():
-    """Forget everything a forward pass leaves between its calls (the open stage, queued weight gradients, the remembered
+    """Forget everything a forward pass leaves between its calls (the open stage, queued and deferred weight gradients, the remembered
     head sums): called after a forward / backward that ended in an exception, e.g. a refused hipGraph capture."""
     stage_end()
     _UNFLUSHED.clear()
     _HEAD_CACHE.clear()
+    _overlap_clear()
 
 
 def _routed(p):

@@ -424,23 +424,69 @@ def linear_wgrad_into(x, dy, dw, db):
     check(lib().ss_linear_wgrad(_p(x), _p(dy), _p(dw), _p(db), m, k, nout, _stream()), "ss_linear_wgrad")
 
 
-def linear_wgrad_group(items):
+_CAPPED_TILES = {}
+
+
+def _capped_launch_tiles(shapes, cap):
+    """The `launch_tiles` argument of ss_linear_wgrad_group_plan_capped for every problem of a capped launch.  The planner gives a tile
+    4 * cap / launch_tiles shares, i.e. equally long items when every problem has the same m.  For problems of different m the launch's
+    work is stated in tiles of THIS problem's K extent (sum of tiles x K-tiles over the launch / this problem's K-tiles), which makes the
+    items equally long across problems; and of 2 .. 8 rounds the count is taken at which the static deal (workgroup b runs items b,
+    b + grid, ...) ends earliest, an item costing its K-tiles plus about 8 for the pipeline fill and the 256-KiB atomic epilogue."""
+    key = (shapes, cap)
+    if key in _CAPPED_TILES:
+        return _CAPPED_TILES[key]
+    tiles = [lib().ss_linear_wgrad_tiles(k, n) for _, k, n in shapes]
+    kt = [_div_up(m, 64) for m, _, _ in shapes]
+    work = sum(t * b for t, b in zip(tiles, kt))
+    words = np.zeros(8, dtype=np.int64)
+    best = None
+    for rounds in (4, 2, 3, 5, 6, 8):
+        cand = [max(1, _div_up(work * 4, rounds * b)) for b in kt]
+        lengths = []
+        for (m, k, n), lt, t, b in zip(shapes, cand, tiles, kt):
+            if lib().ss_linear_wgrad_group_plan_capped(m, k, n, lt, cap, ctypes.c_void_p(words.ctypes.data)) <= 0:
+                continue
+            shares, per = int(words[7]) & 0xffffffff, int(words[7]) >> 32
+            lengths += [min(per, b - s * per) + 8 for s in range(shares) for _ in range(t)]
+        grid = max(1, min(cap, len(lengths)))
+        span = max(sum(lengths[b::grid]) for b in range(grid)) if lengths else 0
+        if best is None or span < best[0]:
+            best = (span, cand)
+    if len(_CAPPED_TILES) > 64:
+        _CAPPED_TILES.clear()
+    _CAPPED_TILES[key] = best[1]
+    return best[1]
+
+
+def linear_wgrad_group(items, max_workgroups=None, stream=None):
     """ONE launch for many nn.Linear weight gradients.  items: list of (x (m,k) bf16, dy (m,n) bf16, dw (n,k) f32 ZEROED,
-    db (n) f32 ZEROED | None).  Problems the pipeline kernel cannot take are run one by one."""
+    db (n) f32 ZEROED | None).  Problems the pipeline kernel cannot take are run one by one.
+    max_workgroups: run the group on at most that many persistent workgroups (ss_linear_wgrad_group_capped: a workgroup fills a CU, the
+    other CUs stay free for another stream); stream: launch there instead of on the current stream (the caller orders the streams)."""
     if not items:
         return
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return linear_wgrad_group(items, max_workgroups)
     dev = items[0][0].device
     desc = np.zeros((len(items), 8), dtype=np.int64)
     counts = []
     # the CUs are shared out over the output tiles of the whole group (one round of workgroups for the launch)
     launch_tiles = sum(lib().ss_linear_wgrad_tiles(x.shape[1], dy.shape[1]) for x, dy, _, _ in items)
+    if max_workgroups is not None:
+        capped_tiles = _capped_launch_tiles(tuple((x.shape[0], x.shape[1], dy.shape[1]) for x, dy, _, _ in items[:128]), int(max_workgroups))
     for x, dy, dw, db in items:
         _req(x, torch.bfloat16, "x"); _req(dy, torch.bfloat16, "dy", (x.shape[0], dy.shape[1]))
         _req(dw, torch.float32, "dw", (dy.shape[1], x.shape[1]))
         if db is not None:
             _req(db, torch.float32, "db", (dy.shape[1],))
         j = len(counts)
-        nwg = lib().ss_linear_wgrad_group_plan2(x.shape[0], x.shape[1], dy.shape[1], launch_tiles, ctypes.c_void_p(desc[j].ctypes.data))
+        words = ctypes.c_void_p(desc[j].ctypes.data)
+        if max_workgroups is None:
+            nwg = lib().ss_linear_wgrad_group_plan2(x.shape[0], x.shape[1], dy.shape[1], launch_tiles, words)
+        else:
+            nwg = lib().ss_linear_wgrad_group_plan_capped(x.shape[0], x.shape[1], dy.shape[1], capped_tiles[len(counts)], int(max_workgroups), words)
         if nwg <= 0 or j >= 128:
             linear_wgrad_into(x, dy, dw, db)
             continue
@@ -448,8 +494,10 @@ def linear_wgrad_group(items):
         desc[j, 3] = db.data_ptr() if db is not None else 0
         desc[j, 4] = x.shape[0]
         counts.append(nwg)
-    if counts:
+    if counts and max_workgroups is None:
         grouped.launch("ss_linear_wgrad_group", desc[:len(counts)].copy(), grouped.starts(counts), dev)
+    elif counts:
+        grouped.launch("ss_linear_wgrad_group_capped", desc[:len(counts)].copy(), grouped.starts(counts), dev, int(max_workgroups))
 
 
 def linear_wgrad(x, dy, want_bias=False):

@@ -666,6 +666,9 @@ class PointTransformerV3(PointModule):
             plan.ready_event = None
         if self.training:
             self._draw_row_scales(plan.levels, feat.device, *(() if with_dec else (False,)))
+        # the decoder's full-resolution Linear weight gradients may run beside the coarse levels' backward (functional.py) -- not with
+        # a backward cut: its caller starts the exchange of dec0's gradients when the backward leaves dec0
+        SF.wgrad_overlap_arm(self.training and torch.is_grad_enabled() and point.get("backward_cut", None) is None)
         return point, feat, plan
 
     def forward(self, data_dict, perms=None):

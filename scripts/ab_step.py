@@ -69,6 +69,8 @@ def setter(on):
         SF.BLOCK_TAIL_MAX_CHANNELS = 256 if on else 128
     elif which == "block_tail_128":   # ... also at 128 and 256 channels (enc2, enc3, dec2) against the default bound of 64
         SF.BLOCK_TAIL_MAX_CHANNELS = 256 if on else 64
+    elif which == "wgrad_overlap":    # dec0 / dec1 Linear weight gradients as one capped group beside the coarse levels' backward
+        SF.WGRAD_OVERLAP = on         # (SS_WGRAD_OVERLAP_FREE_CUS sets the number of CUs left to the chain)
     elif which == "mask_small":
         import scenesplat_amd.plan as P
         P.CONV_MASK_MIN_SITES = 4096 if on else 16384
