@@ -819,6 +819,34 @@ int ss_spp_labels(const int32_t* seg_indices, int64_t n_vertices, const int32_t*
                   const int32_t* table_label, const int32_t* table_object, const int32_t* size, int n_groups, int64_t n, int empty,
                   int16_t* segment, int16_t* instance, ss_stream_t stream);
 
+/* ---- minimal oriented bounding box and the points inside it (csrc/obb.hip; Open3D's get_minimal_oriented_bounding_box and
+ * get_point_indices_within_bounding_box as preprocess_scannet_gs.py / preprocess_scannetpp_gs.py call them; the definition: DESIGN.md
+ * 8q) -------------------------------------------------------------------------------------------------------------------------------
+ * points (N, 3) f32 on the device, 1 <= N < 2^31.  A box is 15 doubles: center (3), R (3, 3) row-major with the axes as COLUMNS,
+ * extent (3).  Bitmaps are ss_pc_bitmap_words(N) uint32 words, bit r & 31 of word r >> 5 = row r, every word written (bits of rows
+ * >= N are 0): the (1, words) bitmap ss_pc_compact_scan / ss_pc_compact turn into ascending rows.
+ * ss_obb_extremes: dirs (K, 3) f64 on the device, 1 <= K <= 1024.  rows_max[d] / rows_min[d] (K) int32 = the row of the largest /
+ *   smallest fp64 projection p . dirs[d]; equal values go to the lower row (pairs are compared as a whole in both reduction stages, so
+ *   two runs agree); -1 where no projection compares (NaN).  workspace: ss_obb_extremes_workspace_bytes(N, K), else SS_ERR_WORKSPACE.
+ * ss_obb_filter: planes (F, 4) f64 on the device (n . p + d <= 0 inside the polytope), F >= 1; *h_tol a HOST double >= 0 (it travels as
+ *   a kernel argument).  Bit r is CLEARED only when n . p + d < -tol for every plane; a NaN keeps the row.
+ * ss_obb_search: verts (H, 3) f64 hull vertices, tris (T, 3) int32 rows of verts, both on the device.  Candidate 3 t + k: corners a, b,
+ *   c of triangle t cyclically from corner k; u = unit(b - a), w = unit(u x (c - a)), v = unit(w x u), unit(x) = x / sqrt((x0^2 + x1^2) +
+ *   x2^2); q = ((dx * r0 + dy * r1) + dz * r2) per axis r of d = p - a over all H vertices; extent = hi - lo, volume = (e0 * e1) * e2.
+ *   Every operation is rounded on its own (no fma), IEEE square root and division.  volumes (3 T) f64: every candidate's (NaN for a
+ *   triangle with a row outside [0, H) or without an area).  best_index (1) int32: the candidate of least volume, equal volumes go to
+ *   the lowest index, NaN never wins; -1 when none compares.  box (15): center = a + ((u m0 + v m1) + w m2), m = (lo + hi) * 0.5, R = [u
+ *   v w], extent.  No atomics.
+ * ss_obb_within: h_box: a HOST box (kernel arguments).  Bit r is set when |((dx * R[0][k] + dy * R[1][k]) + dz * R[2][k])| <=
+ *   extent[k] * 0.5 for k = 0, 1, 2, d = (double)p - center.  M == 0: SS_OK without a launch. */
+size_t ss_obb_extremes_workspace_bytes(int64_t N, int K);
+int ss_obb_extremes(const float* points, int64_t N, const double* dirs, int K, int32_t* rows_max, int32_t* rows_min, void* workspace,
+                    size_t workspace_bytes, ss_stream_t stream);
+int ss_obb_filter(const float* points, int64_t N, const double* planes, int F, const double* h_tol, uint32_t* bitmap, ss_stream_t stream);
+int ss_obb_search(const double* verts, int H, const int32_t* tris, int T, double* volumes, int32_t* best_index, double* box,
+                  ss_stream_t stream);
+int ss_obb_within(const float* points, int64_t M, const double* h_box, uint32_t* bitmap, ss_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

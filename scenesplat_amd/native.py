@@ -2046,3 +2046,59 @@ def pc_compact(bitmap, M, tile_base, total):
     rows = torch.empty(int(total), dtype=torch.int32, device=bitmap.device)
     check(lib().ss_pc_compact(_p(bitmap), M, bitmap.shape[0], _p(tile_base), _p(rows), int(total), _stream()), "ss_pc_compact")
     return rows
+
+
+# ---- minimal oriented bounding box (csrc/obb.hip) ----------------------------------------------------------------------------------------
+def obb_extremes(points, dirs):
+    """ss_obb_extremes: points (N, 3) f32, dirs (K, 3) f64 -> (rows_max, rows_min) (K,) int32: per direction the row of the largest and
+    of the smallest projection (equal values: the lower row)"""
+    _rows3(points, "points"); _req(dirs, torch.float64, "dirs")
+    N, K = points.shape[0], dirs.shape[0]
+    if dirs.dim() != 2 or dirs.shape[1] != 3 or N < 1 or K < 1:
+        raise RuntimeError(f"obb_extremes: expected dirs (K >= 1, 3) and N >= 1, got {tuple(dirs.shape)}, N = {N}")
+    rows = torch.empty((2, K), dtype=torch.int32, device=points.device)
+    ws = _ws(lib().ss_obb_extremes_workspace_bytes(N, K), points.device)
+    check(lib().ss_obb_extremes(_p(points), N, _p(dirs), K, _p(rows[0]), _p(rows[1]), _p(ws), ws.numel(), _stream()), "ss_obb_extremes")
+    return rows[0], rows[1]
+
+
+def obb_filter(points, planes, tol):
+    """ss_obb_filter: points (N, 3) f32, planes (F, 4) f64, tol: a Python float -> bitmap (1, ceil(N / 32)) int32 words of the rows that
+    are not below every plane by more than tol"""
+    _rows3(points, "points"); _req(planes, torch.float64, "planes")
+    N = points.shape[0]
+    if planes.dim() != 2 or planes.shape[1] != 4 or planes.shape[0] < 1 or N < 1:
+        raise RuntimeError(f"obb_filter: expected planes (F >= 1, 4) and N >= 1, got {tuple(planes.shape)}, N = {N}")
+    bitmap = torch.empty((1, lib().ss_pc_bitmap_words(N)), dtype=torch.int32, device=points.device)
+    h_tol = ctypes.c_double(float(tol))
+    check(lib().ss_obb_filter(_p(points), N, _p(planes), planes.shape[0], ctypes.addressof(h_tol), _p(bitmap), _stream()), "ss_obb_filter")
+    return bitmap
+
+
+def obb_search(verts, tris):
+    """ss_obb_search: verts (H, 3) f64, tris (T, 3) int32 rows of verts -> (volumes (3 T,) f64, best_index (1,) int32, box (15,) f64)"""
+    _req(verts, torch.float64, "verts"); _req(tris, torch.int32, "tris")
+    if verts.dim() != 2 or verts.shape[1] != 3 or tris.dim() != 2 or tris.shape[1] != 3 or verts.shape[0] < 1 or tris.shape[0] < 1:
+        raise RuntimeError(f"obb_search: expected verts (H >= 1, 3) and tris (T >= 1, 3), got {tuple(verts.shape)}, {tuple(tris.shape)}")
+    T = tris.shape[0]
+    volumes = torch.empty(3 * T, dtype=torch.float64, device=verts.device)
+    best = torch.empty(1, dtype=torch.int32, device=verts.device)
+    box = torch.empty(15, dtype=torch.float64, device=verts.device)
+    check(lib().ss_obb_search(_p(verts), verts.shape[0], _p(tris), T, _p(volumes), _p(best), _p(box), _stream()), "ss_obb_search")
+    return volumes, best, box
+
+
+def obb_within(points, box15):
+    """ss_obb_within: points (M >= 1, 3) f32, box15: 15 host doubles (center, R row-major, extent) -> bitmap (1, ceil(M / 32)) int32"""
+    _rows3(points, "points")
+    M = points.shape[0]
+    h_box = (ctypes.c_double * 15)(*[float(v) for v in box15])
+    bitmap = torch.empty((1, lib().ss_pc_bitmap_words(M)), dtype=torch.int32, device=points.device)
+    check(lib().ss_obb_within(_p(points), M, ctypes.addressof(h_box), _p(bitmap), _stream()), "ss_obb_within")
+    return bitmap
+
+
+def bitmap_rows(bitmap, n):
+    """the ascending rows of the set bits of a (1, ceil(n / 32)) bitmap: ss_pc_compact_scan, ONE count read, ss_pc_compact"""
+    tile_base, counts = pc_compact_scan(bitmap, n)
+    return pc_compact(bitmap, n, tile_base, int(counts.cpu()[0]))

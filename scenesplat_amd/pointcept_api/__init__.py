@@ -56,4 +56,9 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".scannetpp_mesh", __name__)
         return module if name == "scannetpp_mesh" else getattr(module, name)
+    # oriented_box (the minimal oriented bounding box of a scan and the Gaussians inside it: `prune_box=` of the three converters)
+    if name in ("oriented_box", "OrientedBox", "minimal_oriented_box", "points_within_box"):
+        import importlib
+        module = importlib.import_module(".oriented_box", __name__)
+        return module if name == "oriented_box" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

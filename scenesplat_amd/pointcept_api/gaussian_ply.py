@@ -18,8 +18,10 @@ Values against the reference:
   profiles/ply_ingest.md), so these two arrays are NOT bit-equal to the reference's; they are the closer ones.  A logit of -100 gives
   the denormal 3.8e-44 the fp64 expression rounds to, where the reference's fp32 sigmoid gives 0.
 * a vertex with `rot_0 == 0` yields an all-zero quaternion, as in the reference (sign(0) = 0); kept, not repaired.
-* the oriented-bounding-box pruning of the ScanNet / HoliCity scripts is not carried over (the HoliCity script computes it and then
-  replaces the mask by all ones).
+* the oriented-bounding-box pruning of the ScanNet / HoliCity scripts is a keyword, `prune_box=0.25` (oriented_box.py: the minimal
+  oriented box of the labelled cloud, grown by 25 cm, keeps the Gaussians inside; every edge of a hull triangle is a candidate frame,
+  Open3D tries one per triangle).  The default None writes every Gaussian (the HoliCity script computes the mask and then replaces
+  it by all ones).
 * directory mode processes the files in sorted order (the reference: listing order).
 
 Only float32 properties at 4-byte offsets have a device form; anything else is a ValueError ("no device form"), never a host fallback."""
@@ -33,6 +35,7 @@ import torch
 
 from .. import native as nv
 from .. import pointops
+from . import oriented_box
 
 PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
@@ -220,6 +223,24 @@ def _gather_byte_rows(src, idx):
     return dst
 
 
+def scan_box(points, margin, device):
+    """the minimal oriented box of a scan's points ((m, 3) float32, numpy or device) grown by margin.  ValueError: no volume."""
+    return oriented_box.minimal_oriented_box(points, device).enlarged(margin)
+
+
+def prune_gaussians(gs, box):
+    """load_gaussian_ply's result without the Gaussians outside `box` (an OrientedBox): -> (the kept Gaussians, still in file order;
+    the kept rows, ascending int32 on the device).  Prints the reference's line."""
+    kept = oriented_box.points_within_box(box, gs["coord"])
+    n = gs["coord"].shape[0]
+    print(f"  Pruned {n - kept.numel()} gaussians by init bounding box.")
+    out = OrderedDict()
+    for k, t in gs.items():
+        rows = _gather_byte_rows(t.reshape(n, int(np.prod(t.shape[1:]))).view(torch.uint8), kept)
+        out[k] = rows.view(t.dtype).view((kept.numel(),) + tuple(t.shape[1:]))
+    return out, kept
+
+
 def _transfer(coord, pc_coord, pc_assets):
     """-> {name: ((n, row_bytes) uint8 device tensor, numpy dtype, trailing shape)}"""
     idx, m = _nearest_rows(coord, pc_coord)
@@ -270,10 +291,14 @@ def _load_features(feat):
     return features.to(torch.float16).numpy()
 
 
-def preprocess_gs(input, output, recursive=False, pc_dir=None, feat=None, device=None):
+def preprocess_gs(input, output, recursive=False, pc_dir=None, feat=None, device=None, prune_box=None):
     """scripts/preprocess_gs.py on the device; with pc_dir (coord.npy + any of segment / normal / instance .npy) the nearest-neighbour
-    label transfer of preprocess_holicity_gs.py, with feat its lang_feat.npy (float16) and valid_feat_mask.npy (int64).  A file that
-    does not parse is reported and skipped.  -> the directories written."""
+    label transfer of preprocess_holicity_gs.py, with feat its lang_feat.npy (float16) and valid_feat_mask.npy (int64).  prune_box = m
+    (the reference's 0.25; needs pc_dir): only the Gaussians inside the minimal oriented box of pc_dir's coord.npy grown by m are
+    written, in file order, and the labels are transferred to those alone; None writes all.  A file that does not parse, or a cloud
+    without a box, is reported and skipped.  -> the directories written."""
+    if prune_box is not None and pc_dir is None:
+        raise ValueError("preprocess_gs: prune_box needs pc_dir (the box is the labelled cloud's)")
     files = collect_ply_files(input, output, recursive)
     if not files:
         print(f"{input}: no .ply file in it")
@@ -284,8 +309,8 @@ def preprocess_gs(input, output, recursive=False, pc_dir=None, feat=None, device
         pc_coord = np.load(os.path.join(pc_dir, "coord.npy"))
         cloud = (pc_coord, OrderedDict((a, np.load(os.path.join(pc_dir, a + ".npy"))) for a in PC_ASSETS
                                        if os.path.exists(os.path.join(pc_dir, a + ".npy"))))
-    lang = _load_features(feat) if feat is not None else None
-    written = []
+    all_lang = _load_features(feat) if feat is not None else None
+    written, box = [], None
     for ply_path, out_dir in files:
         print(f"{ply_path}:")
         try:
@@ -294,8 +319,20 @@ def preprocess_gs(input, output, recursive=False, pc_dir=None, feat=None, device
             print(f"  skipped, it could not be read: {e!r}")
             continue
         n = gs["coord"].shape[0]
+        lang = all_lang
         if lang is not None and lang.shape[0] != n:
             raise ValueError(f"{ply_path}: {n} Gaussians, but {feat} holds {lang.shape[0]} feature rows")
+        if prune_box is not None:
+            try:
+                if box is None:                                           # one cloud, one box
+                    box = scan_box(cloud[0], prune_box, gs["coord"].device)
+            except ValueError as e:
+                print(f"  skipped, it could not be read: {e!r}")
+                continue
+            gs, kept = prune_gaussians(gs, box)
+            n = kept.numel()
+            if lang is not None:
+                lang = lang[kept.cpu().numpy()]
         arrays = OrderedDict((k, gs[k].cpu().numpy()) for k in GS_ASSETS)
         if cloud is not None:
             for name, (rows, dtype, trailing) in _transfer(gs["coord"], *cloud).items():
@@ -318,12 +355,15 @@ def build_parser():
     parser.add_argument("--recursive", action="store_true", help="with a folder: take the checkpoints of its sub-folders too")
     parser.add_argument("--pc_dir", default=None, help="labelled point cloud folder (coord.npy + segment / normal / instance .npy) to transfer from")
     parser.add_argument("--feat", default=None, help="language features of the Gaussians: langfeat.pth holding (features, _), or a .npy")
+    parser.add_argument("--prune_box", nargs="?", const=0.25, default=None, type=float,
+                        help="keep only the Gaussians inside the minimal oriented box of --pc_dir's cloud grown by this margin (0.25 when no value is given)")
     return parser
 
 
 def main(argv=None):
     cfg = build_parser().parse_args(argv)
-    done = preprocess_gs(cfg.input, cfg.output, recursive=cfg.recursive, pc_dir=cfg.pc_dir, feat=cfg.feat)
+    done = preprocess_gs(cfg.input, cfg.output, recursive=cfg.recursive, pc_dir=cfg.pc_dir, feat=cfg.feat,
+                         **({} if cfg.prune_box is None else dict(prune_box=cfg.prune_box)))
     print(f"{len(done)} scene folder(s) written")
     return 0 if done else 1
 

@@ -15,8 +15,9 @@ the nearest mesh vertex): the same file names, dtypes, shapes and bytes.
 
 Values against the reference: every array is bit for bit the reference's, except what `load_gaussian_ply` documents for `scale` and
 `opacity` of the checkpoint.  Deviations:
-* the oriented-bounding-box pruning of preprocess_scannet_gs.py (open3d's `get_minimal_oriented_bounding_box` plus 25 cm) is not carried
-  over: every Gaussian of the checkpoint is written (gaussian_ply.py takes the same stance).
+* the oriented-bounding-box pruning of preprocess_scannet_gs.py (open3d's `get_minimal_oriented_bounding_box` plus 25 cm) is the
+  keyword `prune_box=0.25` (oriented_box.py): the box of least volume among the frames of ALL edges of the hull's triangles, where
+  Open3D tries one edge per triangle in Qhull's vertex order; never larger than Open3D's.  The default None writes every Gaussian.
 * the label table, the two valid-id lists and the split lists are arguments: the reference reads them from its `meta_data` folder, this
   package ships none of them (they come with the ScanNet download).
 * `gs_root/<scene>/ckpts/*.ply`: the first in sorted order (the reference: the first in listing order).
@@ -36,7 +37,7 @@ import numpy as np
 import torch
 
 from .. import native as nv
-from .gaussian_ply import GS_ASSETS, MAX_HEADER, PLY_TYPES, _load_features, _nearest_rows, load_gaussian_ply
+from .gaussian_ply import GS_ASSETS, MAX_HEADER, PLY_TYPES, _load_features, _nearest_rows, load_gaussian_ply, prune_gaussians, scan_box
 
 CLOUD_FILE_PFIX = "_vh_clean_2"
 SEGMENTS_FILE_PFIX = ".0.010000.segs.json"
@@ -364,12 +365,14 @@ def preprocess_scannet(dataset_root, output_root, labels_tsv, class_ids20, class
 
 
 def preprocess_scannet_gs(dataset_root, output_root, gs_root, labels_tsv, class_ids20, class_ids200, train_list, val_list, feat_root=None,
-                          feat_only=False, skip_feat=False, device=None):
+                          feat_only=False, skip_feat=False, device=None, prune_box=None):
     """preprocess_scannet_gs.py on the device: per scene the checkpoint gs_root/<scene>/ckpts/*.ply through load_gaussian_ply, the nearest
     mesh vertex per Gaussian (hash-grid 1-NN; equal distances: the lower row), and into output_root/train|val|test/<scene>/ the five
     Gaussian assets, normal.npy (the 'gs' form normals of the nearest vertex), for a train or val scene segment20 / segment200 /
     instance .npy (int16), and with feat_root lang_feat.npy (fp16) and valid_feat_mask.npy (int64).  feat_only is accepted and ignored,
-    as in the reference.  No bounding-box pruning.  -> the directories written."""
+    as in the reference.  prune_box = m (the reference's 0.25): only the Gaussians inside the minimal oriented box of the scan's
+    vertices grown by m are kept, in file order, before the nearest-vertex search; every array written holds the kept rows.  None
+    writes all.  A scan whose vertices span no volume is skipped.  -> the directories written."""
     tables = scannet_label_tables(labels_tsv, class_ids20, class_ids200)
     train_scenes, val_scenes = _scene_list(train_list), _scene_list(val_list)
     dev = _device(device)
@@ -387,6 +390,10 @@ def preprocess_scannet_gs(dataset_root, output_root, gs_root, labels_tsv, class_
             if mesh["coord"].shape[0] == 0:
                 raise ValueError(f"{mesh_path}: no vertices")
             gs = load_gaussian_ply(candidates[0], dev)
+            n_file = gs["coord"].shape[0]
+            kept = None
+            if prune_box is not None:
+                gs, kept = prune_gaussians(gs, scan_box(mesh["coord"], prune_box, dev))
             n = gs["coord"].shape[0]
             arrays = OrderedDict((k, gs[k].cpu().numpy()) for k in GS_ASSETS)
             with torch.cuda.device(dev):
@@ -399,8 +406,10 @@ def preprocess_scannet_gs(dataset_root, output_root, gs_root, labels_tsv, class_
                         arrays[name] = t.cpu().numpy()
             if feat_root is not None and not skip_feat:
                 lang = _load_features(os.path.join(os.fspath(feat_root), scene_id, "langfeat.pth"))
-                if lang.shape[0] != n:
-                    raise ValueError(f"{scene_id}: {n} Gaussians, but the features hold {lang.shape[0]} rows")
+                if lang.shape[0] != n_file:
+                    raise ValueError(f"{scene_id}: {n_file} Gaussians, but the features hold {lang.shape[0]} rows")
+                if kept is not None:
+                    lang = lang[kept.cpu().numpy()]
                 arrays["valid_feat_mask"] = np.any(lang != 0.0, axis=1).astype(np.int64)
                 arrays["lang_feat"] = lang
         except (ValueError, KeyError, OSError) as e:
@@ -422,6 +431,8 @@ def build_parser():
     parser.add_argument("--feat_root", default=None, help="folder with <scene>/langfeat.pth language features (with --gs_root)")
     parser.add_argument("--feat_only", action="store_true", help="accepted and ignored, as in the reference")
     parser.add_argument("--skip_feat", action="store_true", help="do not write the language features")
+    parser.add_argument("--prune_box", nargs="?", const=0.25, default=None, type=float,
+                        help="with --gs_root: keep only the Gaussians inside the scan's minimal oriented box grown by this margin (0.25 when no value is given)")
     parser.add_argument("--parse_normals", default=True, type=bool, help="whether to write normal.npy (point-cloud form)")
     parser.add_argument("--num_workers", default=1, type=int, help="accepted and ignored: the device does the work")
     parser.add_argument("--labels_tsv", required=True, help="scannetv2-labels.combined.tsv")
@@ -438,7 +449,7 @@ def main(argv=None):
                   val_list=cfg.val_list)
     if cfg.gs_root is not None:
         done = preprocess_scannet_gs(cfg.dataset_root, cfg.output_root, cfg.gs_root, feat_root=cfg.feat_root, feat_only=cfg.feat_only,
-                                     skip_feat=cfg.skip_feat, **common)
+                                     skip_feat=cfg.skip_feat, **({} if cfg.prune_box is None else dict(prune_box=cfg.prune_box)), **common)
     else:
         done = preprocess_scannet(cfg.dataset_root, cfg.output_root, parse_normals=cfg.parse_normals, **common)
     print(f"{len(done)} scene folder(s) written")

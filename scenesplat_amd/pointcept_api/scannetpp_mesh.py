@@ -19,8 +19,9 @@ Values against the reference: `coord`, `color` (Open3D holds c / 255.0; `(c / 25
 unnormalised cross products of the incident faces added in face order, once per corner, a division by the fp64 norm where it is above
 zero, one rounding to fp32), restated in numpy by tests/golden/make_golden_scannetpp.py: Open3D itself is not part of this package's
 tests.  Deviations:
-* the oriented-bounding-box pruning of preprocess_scannetpp_gs.py (open3d's `get_minimal_oriented_bounding_box` plus 25 cm) is not
-  carried over: every Gaussian of the checkpoint is written (scannet_mesh.py and gaussian_ply.py take the same stance).
+* the oriented-bounding-box pruning of preprocess_scannetpp_gs.py (open3d's `get_minimal_oriented_bounding_box` plus 25 cm) is the
+  keyword `prune_box=0.25` (oriented_box.py): the box of least volume among the frames of ALL edges of the hull's triangles, where
+  Open3D tries one edge per triangle in Qhull's vertex order; never larger than Open3D's.  The default None writes every Gaussian.
 * the checkpoint arrays are `load_gaussian_ply`'s: the reference's ScanNet++ script computes `quat` and `color` through fp64
   intermediates, so last-bit differences are possible (counted on the fixture: profiles/scannetpp.md), and `scale` / `opacity` are what
   gaussian_ply.py documents.
@@ -45,7 +46,7 @@ import numpy as np
 import torch
 
 from .. import native as nv
-from .gaussian_ply import GS_ASSETS, _gather_byte_rows, _load_features, _nearest_rows, load_gaussian_ply
+from .gaussian_ply import GS_ASSETS, _gather_byte_rows, _load_features, _nearest_rows, load_gaussian_ply, prune_gaussians, scan_box
 from .scannet_mesh import _save, load_ply_mesh, mesh_columns, read_mesh_header  # noqa: F401  (the mesh reader is shared)
 
 MESH_FILE = "mesh_aligned_0.05.ply"
@@ -198,23 +199,29 @@ def _checkpoint(gs_root, name):
     return os.path.join(folders[0], CHECKPOINT)
 
 
+def _too_few(valid):
+    with np.errstate(invalid="ignore"):
+        return bool(np.float64(valid.sum()) / np.float64(valid.size) < 0.5)
+
+
 def _features(feat_root, name):
     """-> (lang_feat float16, valid_feat_mask int64, whether under half of the rows hold a feature)"""
     lang = _load_features(os.path.join(os.fspath(feat_root), name, "langfeat.pth"))
     valid = np.any(lang != 0.0, axis=1).astype(int)
-    with np.errstate(invalid="ignore"):
-        too_few = bool(np.float64(valid.sum()) / np.float64(valid.size) < 0.5)
-    return lang, valid, too_few
+    return lang, valid, _too_few(valid)
 
 
 def preprocess_scannetpp_gs(dataset_root, gs_root, pc_root, output_root, feat_root=None, feat_only=False, skip_feat=False, scenes_list=None,
-                            device=None):
+                            device=None, prune_box=None):
     """preprocess_scannetpp_gs.py on the device: per scene the checkpoint <gs_root>/**/<*scene>/ckpts/point_cloud_30000.ply through
     load_gaussian_ply, the nearest row of pc_root/<split>/<scene>/coord.npy per Gaussian (hash-grid 1-NN; equal distances: the lower
     row), and into output_root/<split>/<scene>/ the five Gaussian assets, normal.npy and, for train and val, segment.npy and
     instance.npy: the rows of the point-cloud folder's arrays, gathered.  With feat_root (and not skip_feat) lang_feat.npy (fp16) and
     valid_feat_mask.npy (int64), unless under half of the rows hold a feature: the scene is then reported among the skipped and gets no
-    feature files.  feat_only writes the feature files alone.  No bounding-box pruning.
+    feature files.  feat_only writes the feature files alone.  prune_box = m (the reference's 0.25): only the Gaussians inside the
+    minimal oriented box of the point-cloud folder's coord.npy grown by m are kept, in file order, before the nearest-row search; every
+    array written holds the kept rows, and the half-valid rule looks at the kept rows (the reference's order).  feat_only never prunes,
+    as in the reference.  None writes all.  A cloud that spans no volume: the scene is skipped.
     -> (the directories written, the scene names skipped for their features)."""
     dev = _device(device)
     written, skipped = [], []
@@ -223,26 +230,40 @@ def preprocess_scannetpp_gs(dataset_root, gs_root, pc_root, output_root, feat_ro
         out_dir = os.path.join(os.fspath(output_root), split, name)
         pc_dir = os.path.join(os.fspath(pc_root), split, name)
         try:
-            arrays = OrderedDict()
-            if feat_root is not None and (feat_only or not skip_feat):
-                lang, valid, too_few = _features(feat_root, name)
+            arrays, feats = OrderedDict(), None
+            pruning = prune_box is not None and not feat_only
+
+            def take_features(lang, valid, too_few):
                 if too_few:
                     print(f"  valid language feature percent too low, skipping the features of scene {name}")
                     skipped.append(name)
                 else:
                     arrays["valid_feat_mask"], arrays["lang_feat"] = valid, lang
+
+            if feat_root is not None and (feat_only or not skip_feat):
+                feats = _features(feat_root, name)
+                if not pruning:
+                    take_features(*feats)
             if not feat_only:
                 gs = load_gaussian_ply(_checkpoint(gs_root, name), dev)
                 n = gs["coord"].shape[0]
-                if "lang_feat" in arrays and arrays["lang_feat"].shape[0] != n:
-                    raise ValueError(f"{name}: {n} Gaussians, but the features hold {arrays['lang_feat'].shape[0]} rows")
+                have = arrays["lang_feat"] if "lang_feat" in arrays else feats[0] if pruning and feats is not None else None
+                if have is not None and have.shape[0] != n:
+                    raise ValueError(f"{name}: {n} Gaussians, but the features hold {have.shape[0]} rows")
+                pc_coord = np.load(os.path.join(pc_dir, "coord.npy"))
+                if pruning:
+                    gs, kept = prune_gaussians(gs, scan_box(pc_coord, prune_box, dev))
+                    n = kept.numel()
+                    if feats is not None:                                # the half-valid rule on the kept rows
+                        rows = kept.cpu().numpy()
+                        take_features(feats[0][rows], feats[1][rows], _too_few(feats[1][rows]))
                 arrays.update((k, gs[k].cpu().numpy()) for k in GS_ASSETS)
                 pc = OrderedDict(normal=np.load(os.path.join(pc_dir, "normal.npy")))
                 if split != "test":
                     pc["instance"] = np.load(os.path.join(pc_dir, "instance.npy"))
                     pc["segment"] = np.load(os.path.join(pc_dir, "segment.npy"))
                 with torch.cuda.device(dev):
-                    nearest, m = _nearest_rows(gs["coord"], np.load(os.path.join(pc_dir, "coord.npy")))
+                    nearest, m = _nearest_rows(gs["coord"], pc_coord)
                     for k, a in pc.items():
                         if a.shape[0] != m:
                             raise ValueError(f"{name}: {k}.npy has {a.shape[0]} rows, coord.npy has {m}")
@@ -274,6 +295,8 @@ def build_parser():
     parser.add_argument("--feat_only", action="store_true", help="write the language features only")
     parser.add_argument("--skip_feat", action="store_true", help="do not write the language features")
     parser.add_argument("--scenes_list", default=None, help="text file of the scenes to process")
+    parser.add_argument("--prune_box", nargs="?", const=0.25, default=None, type=float,
+                        help="with --gs_root: keep only the Gaussians inside the minimal oriented box of the point cloud grown by this margin (0.25 when no value is given)")
     return parser
 
 
@@ -284,7 +307,8 @@ def main(argv=None):
         if cfg.pc_root is None:
             parser.error("--gs_root needs --pc_root")
         done, _ = preprocess_scannetpp_gs(cfg.dataset_root, cfg.gs_root, cfg.pc_root, cfg.output_root, feat_root=cfg.feat_root,
-                                          feat_only=cfg.feat_only, skip_feat=cfg.skip_feat, scenes_list=cfg.scenes_list)
+                                          feat_only=cfg.feat_only, skip_feat=cfg.skip_feat, scenes_list=cfg.scenes_list,
+                                          **({} if cfg.prune_box is None else dict(prune_box=cfg.prune_box)))
     else:
         done = preprocess_scannetpp(cfg.dataset_root, cfg.output_root, ignore_index=cfg.ignore_index, scenes=cfg.scenes_list)
     print(f"{len(done)} scene folder(s) written")
