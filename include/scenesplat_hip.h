@@ -847,6 +847,42 @@ int ss_obb_search(const double* verts, int H, const int32_t* tris, int T, double
                   ss_stream_t stream);
 int ss_obb_within(const float* points, int64_t M, const double* h_box, uint32_t* bitmap, ss_stream_t stream);
 
+/* ---- PCA colours of a feature matrix (csrc/feature_pca.hip; the reference's tools/visualize_features_pca.py; the definition:
+ * DESIGN.md 8r) ------------------------------------------------------------------------------------------------------------------
+ * x (N, D) on the device, rows contiguous, dtype SS_DTYPE_F32 / SS_DTYPE_BF16 / SS_DTYPE_F16; 1 <= N < 2^31, 1 <= D <= SS_PCA_MAX_DIM
+ * (any D: edge tiles are padded in the kernels; rows are read with 16- / 8-byte accesses when D % 4 == 0 and x is aligned to them).
+ * shift (D) f32 on the device or NULL (zeros).  x - shift is the fp32 difference: ONE rounding of the exact value.  No float atomics:
+ * sums that cross a workgroup go through per-workgroup partials in the workspace, added in index order, so two runs agree bit for bit.
+ * A workspace below the size its *_workspace_bytes function names: SS_ERR_WORKSPACE.
+ * ss_pca_col_sums: sums (D) f64 = sum_r ((double)x[r][d] - (double)shift[d]).
+ * ss_pca_gram: gram (D, D) f64 = (x - shift)^T (x - shift), both triangles (pairs ti <= tj of 128-column tiles are computed, the lower
+ *   triangle is their mirror).  Products on v_mfma_f32_32x32x2_f32: an entry is a sum of fp32 fmaf chains over at most
+ *   SS_PCA_GRAM_CHAIN consecutive rows each (in row order, starting at multiples of SS_PCA_GRAM_CHAIN), added in fp64.  Rows are staged
+ *   SS_PCA_GRAM_ROWS at a time and shared out in runs of ss_pca_gram_share_rows(N, D) rows (a multiple of SS_PCA_GRAM_CHAIN, at least
+ *   SS_PCA_GRAM_SHARE_MIN) to ceil(N / that) workgroups per tile pair.
+ * ss_pca_project: comp (k, D) f32, off (k) f32 or NULL, k = 1..3, k <= D.  y (N, k) f32 = sum_d (x[r][d] - shift[d]) * comp[c][d] (fp32
+ *   fmaf, a fixed order) - off[c]; extremes (2 k) f32: the k minima, then the k maxima, of the written y (fminf / fmaxf: a NaN is
+ *   skipped).  A workgroup takes rows in blocks of SS_PCA_PROJECT_ROWS.
+ * ss_pca_colors: colors (N, 3) f32 from y (N, k) and extremes (2 k): p = min(max((y - mn) / r, 0), 1), r = mx - mn, r = 1 where r == 0,
+ *   every operation rounded on its own; k = 3: p; k = 2: (p0, p1, 0.5); k = 1: (p0, p0, p0). */
+enum { SS_DTYPE_F16 = 2 };
+#define SS_PCA_MAX_DIM 1024
+#define SS_PCA_GRAM_CHAIN 256
+#define SS_PCA_GRAM_ROWS 32
+#define SS_PCA_GRAM_SHARE_MIN 512
+#define SS_PCA_PROJECT_ROWS 256
+size_t ss_pca_col_sums_workspace_bytes(int64_t N, int D);
+int ss_pca_col_sums(const void* x, int dtype, int64_t N, int D, const float* shift, double* sums, void* workspace, size_t workspace_bytes,
+                    ss_stream_t stream);
+size_t ss_pca_gram_workspace_bytes(int64_t N, int D);
+int64_t ss_pca_gram_share_rows(int64_t N, int D);
+int ss_pca_gram(const void* x, int dtype, int64_t N, int D, const float* shift, double* gram, void* workspace, size_t workspace_bytes,
+                ss_stream_t stream);
+size_t ss_pca_project_workspace_bytes(int64_t N);
+int ss_pca_project(const void* x, int dtype, int64_t N, int D, const float* shift, const float* comp, const float* off, int k, float* y,
+                   float* extremes, void* workspace, size_t workspace_bytes, ss_stream_t stream);
+int ss_pca_colors(const float* y, const float* extremes, int64_t N, int k, float* colors, ss_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2102,3 +2102,83 @@ def bitmap_rows(bitmap, n):
     """the ascending rows of the set bits of a (1, ceil(n / 32)) bitmap: ss_pc_compact_scan, ONE count read, ss_pc_compact"""
     tile_base, counts = pc_compact_scan(bitmap, n)
     return pc_compact(bitmap, n, tile_base, int(counts.cpu()[0]))
+
+
+# ---- PCA colours of a feature matrix (csrc/feature_pca.hip, DESIGN.md 8r) --------------------------------------------------------
+PCA_MAX_DIM, PCA_GRAM_CHAIN, PCA_GRAM_ROWS = _C["SS_PCA_MAX_DIM"], _C["SS_PCA_GRAM_CHAIN"], _C["SS_PCA_GRAM_ROWS"]
+PCA_GRAM_SHARE_MIN, PCA_PROJECT_ROWS = _C["SS_PCA_GRAM_SHARE_MIN"], _C["SS_PCA_PROJECT_ROWS"]
+_PCA_DTYPES = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: _C["SS_DTYPE_F16"]}
+
+
+def _pca_x(x, shift=None):
+    _req(x, None, "features")
+    if x.dim() != 2 or x.dtype not in _PCA_DTYPES or x.shape[0] < 1 or not 1 <= x.shape[1] <= PCA_MAX_DIM:
+        raise RuntimeError(f"features: expected (N >= 1, 1 <= D <= {PCA_MAX_DIM}) float32 / float16 / bfloat16, got "
+                           f"{tuple(x.shape)} {x.dtype}")
+    if shift is not None:
+        _req(shift, torch.float32, "shift", (x.shape[1],))
+    return x.shape[0], x.shape[1], _PCA_DTYPES[x.dtype]
+
+
+def _pca_ws(workspace, nbytes, device):
+    if workspace is None:
+        return _ws(nbytes, device)
+    _req(workspace, torch.uint8, "workspace")
+    return workspace
+
+
+def pca_col_sums(x, shift=None, workspace=None):
+    """ss_pca_col_sums: x (N, D) f32 / f16 / bf16, shift (D,) f32 or None -> (D,) f64 sums of (double)x - (double)shift"""
+    N, D, dt = _pca_x(x, shift)
+    sums = torch.empty(D, dtype=torch.float64, device=x.device)
+    ws = _pca_ws(workspace, lib().ss_pca_col_sums_workspace_bytes(N, D), x.device)
+    check(lib().ss_pca_col_sums(_p(x), dt, N, D, _p(shift), _p(sums), _p(ws), ws.numel(), _stream()), "ss_pca_col_sums")
+    return sums
+
+
+def pca_gram_workspace_bytes(N, D):
+    return int(lib().ss_pca_gram_workspace_bytes(N, D))
+
+
+def pca_gram_share_rows(N, D):
+    """the rows one workgroup of ss_pca_gram takes at this shape (a multiple of PCA_GRAM_CHAIN, at least PCA_GRAM_SHARE_MIN)"""
+    return int(lib().ss_pca_gram_share_rows(N, D))
+
+
+def pca_gram(x, shift=None, workspace=None):
+    """ss_pca_gram: -> (D, D) f64 = (x - shift)^T (x - shift), both triangles; workspace: a uint8 tensor of
+    pca_gram_workspace_bytes(N, D) bytes (None: allocated here)"""
+    N, D, dt = _pca_x(x, shift)
+    gram = torch.empty((D, D), dtype=torch.float64, device=x.device)
+    ws = _pca_ws(workspace, pca_gram_workspace_bytes(N, D), x.device)
+    check(lib().ss_pca_gram(_p(x), dt, N, D, _p(shift), _p(gram), _p(ws), ws.numel(), _stream()), "ss_pca_gram")
+    return gram
+
+
+def pca_project(x, comp, shift=None, off=None, workspace=None):
+    """ss_pca_project: comp (k, D) f32, off (k,) f32 or None -> (y (N, k) f32 = (x - shift) comp^T - off, extremes (2, k) f32: the minima
+    and the maxima of y)"""
+    N, D, dt = _pca_x(x, shift)
+    _req(comp, torch.float32, "comp")
+    if comp.dim() != 2 or comp.shape[1] != D or not 1 <= comp.shape[0] <= min(3, D):
+        raise RuntimeError(f"pca_project: expected comp (1 <= k <= min(3, D), {D}), got {tuple(comp.shape)}")
+    k = comp.shape[0]
+    if off is not None:
+        _req(off, torch.float32, "off", (k,))
+    y = torch.empty((N, k), dtype=torch.float32, device=x.device)
+    ext = torch.empty((2, k), dtype=torch.float32, device=x.device)
+    ws = _pca_ws(workspace, lib().ss_pca_project_workspace_bytes(N), x.device)
+    check(lib().ss_pca_project(_p(x), dt, N, D, _p(shift), _p(comp), _p(off), k, _p(y), _p(ext), _p(ws), ws.numel(), _stream()),
+          "ss_pca_project")
+    return y, ext
+
+
+def pca_colors(y, extremes):
+    """ss_pca_colors: y (N, k) f32, extremes (2, k) f32 -> (N, 3) f32 colours"""
+    _req(y, torch.float32, "y")
+    if y.dim() != 2 or y.shape[0] < 1 or not 1 <= y.shape[1] <= 3:
+        raise RuntimeError(f"pca_colors: expected y (N >= 1, 1..3), got {tuple(y.shape)}")
+    _req(extremes, torch.float32, "extremes", (2, y.shape[1]))
+    colors = torch.empty((y.shape[0], 3), dtype=torch.float32, device=y.device)
+    check(lib().ss_pca_colors(_p(y), _p(extremes), y.shape[0], y.shape[1], _p(colors), _stream()), "ss_pca_colors")
+    return colors

@@ -61,4 +61,9 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".oriented_box", __name__)
         return module if name == "oriented_box" else getattr(module, name)
+    # feature_pca (PCA colours of a feature matrix on the device: `save_pca=` of the tester), likewise for its command line
+    if name in ("feature_pca", "pca_colors", "fit_pca"):
+        import importlib
+        module = importlib.import_module(".feature_pca", __name__)
+        return module if name == "feature_pca" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

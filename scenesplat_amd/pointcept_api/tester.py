@@ -6,7 +6,9 @@ tools/test.py reaches it,
 Per scene the prediction stays on the device from the fragments to the counts: fused scan + accumulate (csrc/scan.hip), top-k /
 threshold / label mapping / pred[inverse] (ss_vocab_finish), kNN-grid neighbour voting + majority vote, per-instance voting
 (ss_cluster_vote), intersection / union / target (ss_seg_iou).  It leaves the device once, for the files the reference writes:
-`{name}_pred.npy`, `submit/{name}.txt`, `feat/{name}_feat.pth`, `eval_results.txt`.
+`{name}_pred.npy`, `submit/{name}.txt`, `feat/{name}_feat.pth`, `eval_results.txt` -- and, with `save_pca` beside `save_feat`, the PCA
+colours of the saved features, `feat/{name}_pca_colors.npy` (feature_pca.py; not in the reference's tester: its
+tools/visualize_features_pca.py computes them from the saved file).
 
 Differences from the reference, on purpose:
   * datasets are out of scope: `test_loader` is injected (any sized iterable of `[d]` or `d`, see `ZeroShotSemSegTester.test`);
@@ -132,7 +134,7 @@ class ZeroShotSemSegTester(TesterBase):
 
     def __init__(self, cfg, model=None, test_loader=None, verbose=True, class_names=None, text_embeddings=None,
                  excluded_classes=None, enable_voting=False, vote_k=25, confidence_threshold=0.1, ignore_index=-1, save_feat=False,
-                 skip_eval=False, pred_label_mapping=None, index=None, logger=None):
+                 skip_eval=False, pred_label_mapping=None, index=None, logger=None, save_pca=False):
         super().__init__(cfg, model, test_loader, verbose, index=index, logger=logger)
         if index is not None:                              # multi-dataset testing
             cfg = copy.copy(cfg)
@@ -144,6 +146,7 @@ class ZeroShotSemSegTester(TesterBase):
         self.vote_k = tc.get("vote_k", vote_k)
         self.confidence_threshold = tc.get("confidence_threshold", confidence_threshold)
         self.save_feat = tc.get("save_feat", save_feat)
+        self.save_pca = tc.get("save_pca", save_pca)       # with save_feat: feat/{name}_pca_colors.npy beside the features (feature_pca.py)
         self.skip_eval = tc.get("skip_eval", skip_eval)
         self.pred_label_mapping = tc.get("pred_label_mapping", pred_label_mapping)
         self.ignore_index = ignore_index
@@ -213,6 +216,11 @@ class ZeroShotSemSegTester(TesterBase):
             final = F.normalize(feats, p=2, dim=1)
             if inverse is not None:
                 final = final[inverse]
+            if self.save_pca:                              # on the device tensor itself: the colours the tool gives on the saved file
+                from .feature_pca import pca_colors
+                pca_path = feat_save_path[:-len("_feat.pth")] + "_pca_colors.npy"
+                np.save(pca_path, pca_colors(final)["colors"].cpu().numpy())
+                self.log(f"Saved PCA colors to {pca_path}")
             torch.save(final.cpu(), feat_save_path)
             self.log(f"Saved pred feature with shape {tuple(final.shape)} to {feat_save_path}")
         if self.skip_eval:
