@@ -325,6 +325,16 @@ int ss_subm_conv_wgrad_pipe_walk(const void* in, const void* dout, const int32_t
                                  const int32_t* blk_count, const int32_t* blk_list, float* dweight, int64_t n, int cin, int cout,
                                  int taps, ss_stream_t stream);
 int ss_subm_conv_wgrad_uses_pipe(int64_t n, int cin, int cout, int taps);
+/* The pipeline weight gradient on a CAPPED grid of min(items, max_workgroups) persistent workgroups (a workgroup fills a CU, so a cap of
+ * CUs - R leaves R CUs to the kernels of another stream).  An item is what a workgroup is in ss_subm_conv_wgrad_pipe (K share, tap,
+ * output tile); the workgroups draw item ids from `counter`, ONE int32 that must be zero when the kernel starts (zero it on `stream`
+ * in front of every launch; the launch leaves items + workgroups in it).  nbr: the rulebook (taps, n), in walk order when walk != 0
+ * (see ss_subm_conv_wgrad_pipe_walk).  min_per: K-tiles of 64 sites per share, 0 = what the plain launch takes.  dweight ZERO on entry.
+ * ss_subm_conv_wgrad_pipe_items: the item count of such a launch (host arithmetic, no launch; 0 = shape not eligible). */
+int ss_subm_conv_wgrad_pipe_capped(const void* in, const void* dout, const int32_t* nbr, const int32_t* rowperm,
+                                   const int32_t* blk_count, const int32_t* blk_list, float* dweight, int32_t* counter, int64_t n,
+                                   int cin, int cout, int taps, int walk, int min_per, int max_workgroups, ss_stream_t stream);
+int64_t ss_subm_conv_wgrad_pipe_items(int64_t n, int cin, int cout, int taps, int min_per);
 int ss_subm_conv_wgrad_walk(const void* in, const void* dout, const int32_t* nbr, const int32_t* nbr_walk, const int32_t* rowperm,
                             const int32_t* blk_count, const int32_t* blk_list, float* dweight, int64_t n, int cin, int cout,
                             int taps, ss_stream_t stream);

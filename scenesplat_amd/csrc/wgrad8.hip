@@ -390,6 +390,33 @@ k_wgrad8_group_capped(const int64_t* __restrict__ desc, const int32_t* __restric
   }
 }
 
+// The conv weight gradient on a CAPPED grid: gridDim.x = min(items, max_workgroups) persistent workgroups run the items of k_wgrad8<true>
+// (an item = a workgroup id there: share, tap, output tile).  Items differ wildly in length -- a share of a busy tap is up to 160
+// K-tiles, most items of the sparse taps are empty -- so they are handed out by a TICKET instead of a static stride: thread 0 takes
+// atomicAdd(counter, 1) on an int32 the caller zeroed, and the id travels through LDS with a barrier on each side (the second keeps
+// thread 0 from overwriting it for the next item before everybody has read it).  Nothing waits on another workgroup.
+// w8_body<true> in a loop, as above: the early return (an empty share; uniform over the workgroup) skips the item; inside an item every
+// index chunk opens with a barrier, stages its ids between two barriers, and its K loop passes both wave rows through the same number of
+// barriers (the staggered wave row's extra one in the prologue is made up by the other row's after the loop); a wave leaves the K loop
+// with its own LDS-DMA retired (vmcnt(0)), and the ticket barriers of the next round keep a fast wave from staging ids or rows over
+// what a slow one still reads.  The results are fp32 atomics into a zeroed dW, whose order was never fixed.
+__global__ void __launch_bounds__(512)
+k_wgrad8_conv_capped(const unsigned short* __restrict__ X, const unsigned short* __restrict__ DY, const int32_t* __restrict__ nbr,
+                     const int32_t* __restrict__ rowperm, const int32_t* __restrict__ blk_count,
+                     const int32_t* __restrict__ blk_list, float* __restrict__ dW, int32_t* __restrict__ counter, int n, int Cin,
+                     int Cout, int taps, int ntn, int nblocks_total, int min_per, int ntiles, int nshares, int walk, int total_items) {
+  __shared__ int ticket;
+  for (;;) {
+    if (threadIdx.x == 0) ticket = atomicAdd(counter, 1);
+    __syncthreads();
+    const int L = ticket;
+    __syncthreads();
+    if (L >= total_items) break;
+    w8_body<true>(X, DY, nbr, rowperm, blk_count, blk_list, dW, nullptr, n, Cin, Cout, taps, ntn, nblocks_total, min_per, ntiles,
+                  nshares, L, walk);
+  }
+}
+
 // XCD-aware tile order of the conv weight gradient: default OFF.  Stand-alone it wins (dec0 1.077 -> 1.041 ms, dec1 188 -> 184 us, two
 // repetitions), inside the step it loses (in-process interleaved A/B, scripts/ab_step.py wgrad_xcd: 37.48 ms with, 37.23 without).
 static int w8_xcd_flag = -1;
@@ -414,8 +441,49 @@ static int w8_min_per(int64_t busy_tiles, int64_t est_blocks) {
   return (int)per;
 }
 
+// the conv's share length: the active-block counts live on the device, so it is sized for a tap that is 70 % active, about a third of
+// the taps being busy on surfaces (SS_WGRAD_MINPER overrides)
+static int w8_conv_min_per(int nblocks, int tiles, int taps) {
+  static int env_per = -2;
+  if (env_per == -2) { const char* e = getenv("SS_WGRAD_MINPER"); env_per = e ? atoi(e) : -1; }
+  return env_per > 0 ? env_per : w8_min_per((int64_t)tiles * ((taps + 2) / 3), (int64_t)nblocks * 7 / 10);
+}
+
 static int w8_conv_launch(const void* in, const void* dout, const int32_t* nbr, const int32_t* rowperm, const int32_t* blk_count,
                           const int32_t* blk_list, float* dweight, int64_t n, int cin, int cout, int taps, int walk, hipStream_t stream);
+
+// The same items on min(items, max_workgroups) persistent workgroups (k_wgrad8_conv_capped).  nbr: the rulebook, in walk order when
+// walk != 0; counter: one int32 that is ZERO when the kernel starts (the caller zeroes it on `stream`; a launch leaves items + grid in
+// it); min_per = 0: the share length of the plain launch.
+extern "C" int ss_subm_conv_wgrad_pipe_capped(const void* in, const void* dout, const int32_t* nbr, const int32_t* rowperm,
+                                              const int32_t* blk_count, const int32_t* blk_list, float* dweight, int32_t* counter,
+                                              int64_t n, int cin, int cout, int taps, int walk, int min_per, int max_workgroups,
+                                              hipStream_t stream) {
+  if (n == 0) return SS_OK;
+  if (!ss_wgrad8_ok(n, cin, cout, taps) || !blk_count || !blk_list || !nbr || !counter || min_per < 0 || max_workgroups <= 0)
+    return SS_ERR_ARG;
+  const int nblocks = ss_div_up(n, 64);
+  const int tm = ss_div_up(cout, 256), tn = ss_div_up(cin, 256);
+  if (min_per == 0) min_per = w8_conv_min_per(nblocks, tm * tn, taps);
+  if (min_per > nblocks) min_per = nblocks;           // one share (keeps share * per inside int)
+  const int splits = ss_div_up(nblocks, min_per);
+  const int64_t items = (int64_t)taps * splits * tm * tn;
+  if (items >= (1LL << 30)) return SS_ERR_ARG;
+  const int grid = items < max_workgroups ? (int)items : max_workgroups;
+  SS_LAUNCH(k_wgrad8_conv_capped, dim3((unsigned)grid), dim3(512), 0, stream, (const unsigned short*)in, (const unsigned short*)dout,
+            nbr, rowperm, blk_count, blk_list, dweight, counter, (int)n, cin, cout, taps, tn, nblocks, min_per, tm * tn, splits,
+            walk ? 1 : 0, (int)items);
+  return SS_OK;
+}
+/* the item count of that launch (host arithmetic only), for callers that size a cap against it */
+extern "C" int64_t ss_subm_conv_wgrad_pipe_items(int64_t n, int cin, int cout, int taps, int min_per) {
+  if (n <= 0 || !ss_wgrad8_ok(n, cin, cout, taps) || min_per < 0) return 0;
+  const int nblocks = ss_div_up(n, 64);
+  const int tiles = ss_div_up(cout, 256) * ss_div_up(cin, 256);
+  if (min_per == 0) min_per = w8_conv_min_per(nblocks, tiles, taps);
+  if (min_per > nblocks) min_per = nblocks;
+  return (int64_t)taps * ss_div_up(nblocks, min_per) * tiles;
+}
 
 extern "C" int ss_subm_conv_wgrad_pipe(const void* in, const void* dout, const int32_t* nbr, const int32_t* rowperm,
                                        const int32_t* blk_count, const int32_t* blk_list, float* dweight, int64_t n,
@@ -437,9 +505,7 @@ static int w8_conv_launch(const void* in, const void* dout, const int32_t* nbr, 
   const int tm = ss_div_up(cout, 256), tn = ss_div_up(cin, 256);
   // the active-block counts live on the device: launch enough shares for a fully active tap and let the kernel
   // size them (>= min_per K-tiles each); on surfaces about a third of the taps carry almost all pairs
-  static int env_per = -2;
-  if (env_per == -2) { const char* e = getenv("SS_WGRAD_MINPER"); env_per = e ? atoi(e) : -1; }
-  int min_per = env_per > 0 ? env_per : w8_min_per((int64_t)tm * tn * ((taps + 2) / 3), (int64_t)nblocks * 7 / 10);
+  int min_per = w8_conv_min_per(nblocks, tm * tn, taps);
   int splits = ss_div_up(nblocks, min_per);
   if (ss_wgrad_xcd_order()) walk |= 2;
   dim3 g((unsigned)((int64_t)taps * splits * tm * tn));

@@ -216,13 +216,14 @@ class _SubMConv3dFused(torch.autograd.Function):
     (same kernel, tap-mirrored transposed weights) and wgrad; duplicate voxels handled exactly."""
 
     @staticmethod
-    def forward(ctx, feat, weight, bias, nbr, rowperm, blocks_fn, has_dup, walk_fn=None, dup_fn=None):
+    def forward(ctx, feat, weight, bias, nbr, rowperm, blocks_fn, has_dup, walk_fn=None, dup_fn=None, late=None):
         taps, n = nbr.shape
         cout, cin = weight.shape[0], weight.shape[-1]
         x, w, pad = _pad8(feat.to(torch.bfloat16), bf16_of(weight).reshape(cout, taps, cin))
         x, w = x.contiguous(), w.contiguous()
         ctx.meta = _conv_meta(feat, weight, bias)
         ctx.blocks_fn, ctx.has_dup, ctx.dup_fn = blocks_fn, has_dup, dup_fn
+        ctx.late = late if not pad else None      # (stage, parameter): the weight gradient may run beside the coarse levels' backward
         ctx.wt = mirrored_of(weight) if not pad else None      # dgrad weight kept beside the shadow (functional.register_mirrored)
         ctx.im2col = n <= CONV_IM2COL_MAX_SITES
         # bf16 out under autocast (the next op is a bf16 GEMM); outside autocast (the evaluator's call form) the output
@@ -265,11 +266,17 @@ class _SubMConv3dFused(torch.autograd.Function):
             if ctx.im2col:                                         # x is the saved im2col(x): (n, taps * cin_padded)
                 dw = _mm_f32(g.t(), x).view(w.shape)
             else:
-                dw = nv.subm_conv_wgrad(x, g, nbr, rowperm, _conv_blocks(ctx.blocks_fn, nbr, rowperm), nbr_walk=walk)
+                blocks = _conv_blocks(ctx.blocks_fn, nbr, rowperm)
+                if _conv_wgrad_defers(getattr(ctx, "late", None), x, g, nbr.shape[0], w_dtype):
+                    # nothing downstream reads it: queued, zeroed, and filled on the side stream (_overlap_launch)
+                    dw = nv.zeros_f32(w.numel(), x.device).view(w.shape)
+                    _overlap_queue_conv(ctx.late[1], (x, g, nbr, rowperm, blocks, walk, dw.detach()))
+                else:
+                    dw = nv.subm_conv_wgrad(x, g, nbr, rowperm, blocks, nbr_walk=walk)
             dw = dw[:, :, :cin].reshape(w_shape).to(w_dtype)
         if has_bias and ctx.needs_input_grad[2]:
             db = _bias_grad(g, w_dtype)
-        return dx, dw, db, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None
 
 
 def _split_bf16(t):
@@ -400,7 +407,9 @@ def subm_conv3d(feat, weight, bias, nbr, has_dup=False, compute_dtype=torch.floa
     has_dup: the level holds duplicate voxels (Mix3D batches); dup_fn() -> (sorted keys, order) of the level (plan.Level.dup_runs),
     derived from the rulebook when absent.  Every MFMA path handles duplicates itself (no per-tap detour)."""
     if compute_dtype == torch.bfloat16 and weight.shape[0] % 8 == 0:
-        return _SubMConv3dFused.apply(feat, weight, bias, nbr, rowperm, blocks_fn, has_dup, walk_fn, dup_fn)
+        stage = _STAGE["cur"]
+        late = (stage, weight) if (CONV_WGRAD_OVERLAP and stage is not None and stage.defer) else None
+        return _SubMConv3dFused.apply(feat, weight, bias, nbr, rowperm, blocks_fn, has_dup, walk_fn, dup_fn, late)
     if compute_dtype == "bf16x3":
         if (CONV_F32_MFMA and weight.shape[0] == 32 and weight.shape[-1] <= 32 and feat.is_cuda
                 and (weight.shape[-1] == 32 or not feat.requires_grad)):
@@ -691,21 +700,48 @@ WGRAD_GROUP_MAX_BYTES = int(float(os.environ.get("SS_WGRAD_GROUP_MAX_GIB", "8"))
 # last consecutive such stage the list runs as ONE capped group (ss_linear_wgrad_group_capped) on a side stream, on CUs -
 # WGRAD_OVERLAP_FREE_CUS persistent workgroups -- a workgroup fills a CU, so that many CUs stay free for the chain.  While the group is in
 # flight the small stages HOLD their own grouped launches (128 KiB of LDS per workgroup: they would queue for the few free CUs); the
-# main stream joins the side stream in front of the next large stage, launches what was held, and in any case when the backward ends.
+# main stream joins the side stream in front of the next large stage (WGRAD_OVERLAP_JOIN = "large") or not before the backward ends or
+# the next deferring stage ("end", with the convs in the filler: see below), launches what was held, and in any case when the backward ends.
 # Gradient buffers are handed to autograd at the flush as always, zeroed, and filled later: nothing reads a .grad before the join.  That
 # needs autograd to keep the buffer itself as the parameter's .grad, so a stage whose parameters already have a .grad (gradient
 # accumulation) or gradient hooks launches at its flush as before.
 WGRAD_OVERLAP = os.environ.get("SS_WGRAD_OVERLAP", "1") != "0"
 WGRAD_DEFER_MIN_ROWS = int(os.environ.get("SS_WGRAD_DEFER_MIN_ROWS", "16384"))
-WGRAD_OVERLAP_FREE_CUS = int(os.environ.get("SS_WGRAD_OVERLAP_FREE_CUS", "80"))
-_OVERLAP = {"armed": False, "stages": [], "items": [], "pairs": [], "held": [], "flight": None, "callback": False, "streams": {}}
+# The SubMConv3d weight gradients of the deferring stages (dec0 2 x 1.17 ms, dec1 2 x 0.18 ms of k_wgrad8<true> on every CU, nothing
+# downstream reads them) join the filler: a conv of such a stage that runs the pipeline kernel queues its operands instead of launching,
+# and _overlap_launch runs the queued convs behind the capped Linear group on the side stream, one capped launch each
+# (ss_subm_conv_wgrad_pipe_capped), largest first.  SS_CONV_WGRAD_OVERLAP=0 keeps the Linear overlap alone.
+CONV_WGRAD_OVERLAP = os.environ.get("SS_CONV_WGRAD_OVERLAP", "1") != "0"
+# 80 free CUs and the join in front of enc1 are the best setting for the Linear group alone (profiles/wgrad_overlap.md) and stay the defaults
+# with SS_CONV_WGRAD_OVERLAP=0; with the convs behind the group, 72 and the join at the end are (profiles/conv_wgrad_overlap.md)
+WGRAD_OVERLAP_FREE_CUS = int(os.environ.get("SS_WGRAD_OVERLAP_FREE_CUS", "72" if CONV_WGRAD_OVERLAP else "80"))
+CONV_WGRAD_OVERLAP_MIN_PER = int(os.environ.get("SS_CONV_WGRAD_OVERLAP_MIN_PER", "0"))     # K-tiles per share; 0: the plain launch's
+# Where the main stream joins the side stream.  "large": in front of the next stage of WGRAD_DEFER_MIN_ROWS rows or more (enc1).
+# "end": not before the backward ends or the next DEFERRING stage -- the filler also runs beside enc1, enc0 and the stem, whose grouped
+# launches are held like those of the small stages.
+WGRAD_OVERLAP_JOIN = os.environ.get("SS_WGRAD_OVERLAP_JOIN", "end" if CONV_WGRAD_OVERLAP else "large")
+# Where the filler starts: 0 = when the backward leaves the last deferring stage (behind dec1), k = k stages later (1: behind dec2)
+WGRAD_OVERLAP_START_SKIP = int(os.environ.get("SS_WGRAD_OVERLAP_START_SKIP", "0"))
+# 1: a stage that flushes while the filler is in flight runs its grouped launch on the side stream behind it instead of holding it to the join
+WGRAD_OVERLAP_HELD_SIDE = os.environ.get("SS_WGRAD_OVERLAP_HELD_SIDE", "0") == "1"
+_OVERLAP = {"armed": False, "stages": [], "items": [], "convs": [], "pairs": [], "held": [], "flight": None, "callback": False,
+            "skip": 0, "streams": {}}
 OVERLAP_STATS = {"deferred": 0, "launched": 0, "joined": 0}      # stages deferred, capped launches, joins: call counters
+CONV_OVERLAP_STATS = {"deferred": 0, "capped": 0, "inline": 0}   # convs queued; run capped on the side stream; queued but run plain at the end
+
+
+def overlap_join_due(mode, rows, next_rows, defers, next_defers, min_rows):
+    """Does the main stream join the side stream at the first flush of a stage with `rows` rows, when the backward enters a stage with
+    next_rows rows next (None: this was the last stage)?  defers / next_defers: whether those stages defer their own weight gradients."""
+    if mode == "end":
+        return bool(defers or next_defers)        # (the end of the backward joins in any case: _overlap_finish)
+    return next_rows is None or max(rows, next_rows) >= min_rows
 
 
 def wgrad_overlap_arm(on):
     """Called by the model at the top of a forward: may this forward's backward defer weight gradients?  (The model says no for a
     backward cut, whose caller takes dec0's gradients as final when the backward leaves dec0, and outside training.)"""
-    if _OVERLAP["flight"] is not None or _OVERLAP["items"] or _OVERLAP["held"]:
+    if _OVERLAP["flight"] is not None or _OVERLAP["items"] or _OVERLAP["held"] or _OVERLAP["convs"]:
         _overlap_clear()                          # left by a backward pass that died half way
     _OVERLAP["armed"] = bool(on) and WGRAD_OVERLAP and WGRAD_DEFER_MIN_ROWS > 0
     _OVERLAP["stages"] = []
@@ -715,7 +751,7 @@ def _overlap_clear():
     flight = _OVERLAP["flight"]
     if flight is not None and not torch.cuda.is_current_stream_capturing():
         flight[0].wait_stream(flight[1])          # the operands go back to the main stream's allocator
-    _OVERLAP.update(armed=False, stages=[], items=[], pairs=[], held=[], flight=None, callback=False)
+    _OVERLAP.update(armed=False, stages=[], items=[], convs=[], pairs=[], held=[], flight=None, callback=False, skip=0)
 
 
 def _overlap_alias(stage, q):
@@ -724,10 +760,40 @@ def _overlap_alias(stage, q):
     q = [(x, dy, dw.detach(), db.detach() if db is not None else None) for x, dy, dw, db in q]
     stage.late = stage.late or {}
     stage.late.update({t.data_ptr(): t for _, _, dw, db in q for t in (dw, db) if t is not None})
+    _overlap_callback()
+    return q
+
+
+def _overlap_callback():
     if not _OVERLAP["callback"]:
         _OVERLAP["callback"] = True
         torch.autograd.Variable._execution_engine.queue_callback(_overlap_finish)
-    return q
+
+
+def _conv_wgrad_defers(late, x, g, taps, w_dtype):
+    """May this SubMConv3d weight gradient (bf16 MFMA path, no channel padding) be queued for the side stream?  Its stage defers its
+    Linears, the filler has not started yet, the shape runs the pipeline kernel, and autograd will keep the buffer it is handed as the
+    parameter's .grad (fp32, no hooks, no .grad yet, no graph of the backward, one process)."""
+    if late is None or not (CONV_WGRAD_OVERLAP and _OVERLAP["armed"]) or _OVERLAP["flight"] is not None:
+        return False
+    stage, p = late
+    if not stage.defer or stage.hooked or w_dtype != torch.float32 or p.grad is not None or torch.is_grad_enabled():
+        return False
+    if getattr(p, "_post_accumulate_grad_hooks", None) or p._backward_hooks:
+        return False
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        return False
+    return bool(nv.lib().ss_subm_conv_wgrad_uses_pipe(x.shape[0], x.shape[1], g.shape[1], taps))
+
+
+def _overlap_queue_conv(p, item):
+    """item = (x, g, nbr, rowperm, blocks, nbr_walk | None, alias of the zeroed accumulator).  x is a saved activation and g the
+    gradient the conv was handed by the Linear behind it: once the conv's backward has returned nobody else holds g, so nothing can
+    write into it before the side stream has read it."""
+    _OVERLAP["convs"].append(item)
+    _OVERLAP["pairs"].append((p, item[-1]))
+    CONV_OVERLAP_STATS["deferred"] += 1
+    _overlap_callback()
 
 
 def _overlap_launch():
@@ -740,8 +806,14 @@ def _overlap_launch():
         side = _OVERLAP["streams"][dev] = torch.cuda.Stream(dev)
     side.wait_stream(main)
     cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    nv.linear_wgrad_group(items, max_workgroups=max(1, cus - WGRAD_OVERLAP_FREE_CUS), stream=side)
-    _OVERLAP["flight"] = (main, side, items)      # the operands were allocated on the main stream: kept until the join
+    cap = max(1, cus - WGRAD_OVERLAP_FREE_CUS)
+    nv.linear_wgrad_group(items, max_workgroups=cap, stream=side)
+    convs, _OVERLAP["convs"] = _OVERLAP["convs"], []
+    for x, g, nbr, rowperm, blocks, walk, dw in sorted(convs, key=lambda c: -c[0].shape[0] * c[0].shape[1] * c[1].shape[1]):
+        nv.subm_conv_wgrad_capped(x, g, nbr, rowperm, blocks, out=dw, nbr_walk=walk, max_workgroups=cap,
+                                  min_per=CONV_WGRAD_OVERLAP_MIN_PER, stream=side)
+        CONV_OVERLAP_STATS["capped"] += 1
+    _OVERLAP["flight"] = (main, side, [items, convs])      # the operands were allocated on the main stream: kept until the join
     OVERLAP_STATS["launched"] += 1
 
 
@@ -769,6 +841,10 @@ def _overlap_finish():
         if _OVERLAP["items"]:                     # the chain never left the deferring stages (no smaller stage behind them)
             items, _OVERLAP["items"] = _OVERLAP["items"], []
             nv.linear_wgrad_group(items)
+        convs, _OVERLAP["convs"] = _OVERLAP["convs"], []
+        for x, g, nbr, rowperm, blocks, walk, dw in convs:      # queued, but the filler never started (or had started already)
+            nv.subm_conv_wgrad(x, g, nbr, rowperm, blocks, out=dw, nbr_walk=walk)
+            CONV_OVERLAP_STATS["inline"] += 1
         main = _overlap_join() or cur
         if cur != main:
             cur.wait_stream(main)
@@ -815,12 +891,24 @@ class _WgradStage:
             _OVERLAP["items"] += _overlap_alias(self, q)
             OVERLAP_STATS["deferred"] += 1
             if self.prev is None or not self.prev.defer:
-                _overlap_launch()
+                _OVERLAP["skip"] = WGRAD_OVERLAP_START_SKIP if self.prev is not None else 0
+                if not _OVERLAP["skip"]:
+                    _overlap_launch()
+        elif late_ok and WGRAD_OVERLAP_HELD_SIDE:
+            q = _overlap_alias(self, q)           # behind the filler on the side stream, which first waits for this stage's operands
+            _OVERLAP["flight"][1].wait_stream(torch.cuda.current_stream())
+            nv.linear_wgrad_group(q, stream=_OVERLAP["flight"][1])
+            _OVERLAP["flight"][2].append(q)
         elif late_ok:
             _OVERLAP["held"].append((self, _overlap_alias(self, q)))
         else:
             nv.linear_wgrad_group(q)
-        if flight and first and (self.prev is None or max(self.n_rows, self.prev.n_rows) >= WGRAD_DEFER_MIN_ROWS):
+            if first and not flight and _OVERLAP["items"] and _OVERLAP["skip"] > 0:
+                _OVERLAP["skip"] -= 1             # the filler starts behind this stage (WGRAD_OVERLAP_START_SKIP)
+                if not _OVERLAP["skip"] or self.prev is None or self.prev.defer:
+                    _overlap_launch()
+        if flight and first and overlap_join_due(WGRAD_OVERLAP_JOIN, self.n_rows, self.prev.n_rows if self.prev is not None else None,
+                                                 self.defer, self.prev is not None and self.prev.defer, WGRAD_DEFER_MIN_ROWS):
             _overlap_join()                       # the next stage is a large one again (or this one is: the join is overdue)
         nv.group_partial_sums(r)
 

@@ -314,6 +314,35 @@ def subm_conv_wgrad(x, dout, nbr, rowperm, blocks, out=None, nbr_walk=None):
     return dw
 
 
+def subm_conv_wgrad_capped(x, dout, nbr, rowperm, blocks, out=None, nbr_walk=None, max_workgroups=None, min_per=0, stream=None):
+    """subm_conv_wgrad's result from the pipeline kernel on at most max_workgroups PERSISTENT workgroups (ss_subm_conv_wgrad_pipe_capped:
+    a workgroup fills a CU, the other CUs stay free for another stream; None: one per CU).  The shape must be one the pipeline kernel
+    takes.  out: a ZEROED (cout,taps,cin) f32 accumulator; min_per: K-tiles per share (0: the plain launch's); stream: launch there
+    instead of on the current stream (the caller orders the streams).  The ticket counter is a fresh zero word per call."""
+    if stream is not None:
+        with torch.cuda.stream(stream):
+            return subm_conv_wgrad_capped(x, dout, nbr, rowperm, blocks, out, nbr_walk, max_workgroups, min_per)
+    n, cin = x.shape
+    cout = dout.shape[1]
+    taps = nbr.shape[0]
+    _req(x, torch.bfloat16, "x"); _req(dout, torch.bfloat16, "dout", (n, cout)); _req(nbr, torch.int32, "nbr", (taps, n))
+    if rowperm is not None:
+        _req(rowperm, torch.int32, "rowperm", (n,))
+    cnt, lst = blocks
+    _req(cnt, torch.int32, "blk_count", (taps,)); _req(lst, torch.int32, "blk_list", (taps, (n + 63) // 64))
+    if nbr_walk is not None:
+        _req(nbr_walk, torch.int32, "nbr_walk", (taps, n))
+    if max_workgroups is None:
+        max_workgroups = torch.cuda.get_device_properties(x.device).multi_processor_count
+    dw = torch.zeros((cout, taps, cin), dtype=torch.float32, device=x.device) if out is None else _req(out, torch.float32, "out", (cout, taps, cin))
+    counter = torch.zeros(1, dtype=torch.int32, device=x.device)
+    rule = nbr if nbr_walk is None else nbr_walk
+    check(lib().ss_subm_conv_wgrad_pipe_capped(_p(x), _p(dout), _p(rule), _p(rowperm), _p(cnt), _p(lst), _p(dw), _p(counter), n, cin, cout,
+                                               taps, int(nbr_walk is not None), int(min_per), int(max_workgroups), _stream()),
+          "ss_subm_conv_wgrad_pipe_capped")
+    return dw
+
+
 def subm_f32_weight_layout(w, mirror=False):
     """w (32, taps, c) f32 -> the fp32-MFMA conv's operand layout [tap][cp / 8][2][32][4] (cp = c padded to 16 or 32).
     mirror: the dgrad operand, w'[ci][T-1-t][co] = w[co][t][ci] (needs c == 32)."""
