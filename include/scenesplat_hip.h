@@ -25,6 +25,8 @@
  *   ss_seg_iou                                utils/misc.py:167-179 (intersection_and_union_gpu), hooks/evaluator.py:106-240
  *   ss_aug_bbox ... ss_aug_color             pointcept/datasets/transform.py:446-816,1120-1178 (the per-sample augmentations
  *                                             in front of GridSample: CenterShift ... ChromaticJitter)
+ *   ss_aug_hsv / ss_aug_moments               pointcept/datasets/transform.py:1037-1100 (HueSaturationTranslation), :424-434 (NormalizeCoord)
+ *   ss_instance_boxes / ss_instance_scatter   pointcept/datasets/transform.py:1626-1664 (InstanceParser)
  *   ss_voxel_pick_labelled                    pointcept/datasets/transform.py:1245-1253 (GridSample's pick over pc_coord)
  *   ss_color_chain / ss_voxel_blur            pointcept/datasets/transform.py:820-1032 (RandomColorJitter, RandomColorGrayScale),
  *                                             :60-176 (GSGaussianBlurVoxelOpc)
@@ -518,6 +520,37 @@ int ss_aug_elastic(float* coord, int64_t n, const float* noise, int d0, int d1, 
  * bit 2: c <- clip(c + N * jitter_std * 255, 0, 255), N from noise (n,3) or Philox (as above); then normalize != 0: c / 127.5 - 1 */
 int ss_aug_color(float* color, int64_t n, int flags, const float* h_lo, const float* h_hi, float blend, const float* h_tr,
                  float jitter_std, const float* noise, uint64_t seed, int normalize, ss_stream_t stream);
+/* HueSaturationTranslation (transform.py:1037-1100) on color (n,3), fp32 on the 0..255 scale, in place; h_hue_sat = 2 HOST doubles
+ * {hue_val, sat_ratio} (doubles travel behind a host pointer: the ABI has no double by value).  Per point, in fp64, uncontracted
+ * and in the reference's operation order, with IEEE division:
+ *   rgb -> hsv   v = max, s = (max - min) / max, h = ((bc - gc | 2 + rc - bc | 4 + gc - rc) / 6) % 1 by the ordered branches
+ *                r == max, else g == max, else b; xc = (max - x) / (max - min); max == min gives h = s = 0
+ *   shift        h <- (hue_val + h + 1) % 1, s <- clip(sat_ratio * s, 0, 1); a % 1 is numpy's: fmod, + 1 when negative, and may
+ *                round to exactly 1.0 (sector 6 = sector 0)
+ *   hsv -> rgb   i = uint8(h * 6), f = h * 6 - i, p = v (1 - s), q = v (1 - s f), t = v (1 - s (1 - f)); s == 0: (v, v, v), else by
+ *                i % 6: 1 (q,v,p)  2 (p,v,t)  3 (p,q,v)  4 (t,p,v)  5 (v,p,q)  0 (v,t,p)
+ * and writes the results truncated to integers (the reference's astype("uint8")) back as fp32.  Inputs are on 0..255; outside that
+ * range numpy's cast is undefined and this one saturates to 0 / 255 (NaN -> 0). */
+int ss_aug_hsv(float* color, int64_t n, const double* h_hue_sat, ss_stream_t stream);
+/* NormalizeCoord's reductions over p = A x + b (h_affine = 12 HOST doubles, A row-major then b; NULL: p = x), x (n,3) fp32, in fp64:
+ * out4 = {sum p_x, sum p_y, sum p_z, max |p|^2}, p_i = ((a_i0 x + a_i1 y) + a_i2 z) + b_i and |p|^2 = (p_x^2 + p_y^2) + p_z^2 without
+ * contraction, so the maximum is bit-equal to that expression in numpy.  Deterministic: per-block partials (ss_aug_moments_blocks(n) * 4
+ * doubles) and a one-wave finish, no atomics.  n >= 1. */
+int ss_aug_moments_blocks(int64_t n);
+int ss_aug_moments(const float* x, int64_t n, const double* h_affine, double* partials, double* out4, ss_stream_t stream);
+/* InstanceParser (transform.py:1626-1664).  order / idx_ptr / cluster: what ss_argsort_i64 (stable) and ss_pool_partition wrote for the
+ * rows' instance ids, the rows to ignore keyed past every id: run k < K is instance k and holds rows order[idx_ptr[k] .. idx_ptr[k+1]),
+ * ascending.
+ * ss_instance_boxes: one workgroup per instance; bbox (K,8) = {(max + min) / 2 (3), max - min (3), 0, class} in fp32 with exact min /
+ *   max, class = segment[first row of the run] - #{v in h_vacancy : class > v} (h_vacancy: num_vacancy <= 16 HOST int64, the non-negative
+ *   segment ignore indices); centroid (K,3) = the fp64 sum of the run's coordinates in a fixed tree order / count, rounded once to fp32.
+ *   segment (int64) and coord (n,3) are indexed by row.  K == 0: SS_OK without a launch.
+ * ss_instance_scatter: per row, instance[row] (int64 when instance_is_i64, else int32) <- cluster[row] and instance_centroid[row] <-
+ *   centroid[cluster[row]]; rows of a run >= K get ignore_index in both.  K == 0: every row does (cluster / centroid not looked at). */
+int ss_instance_boxes(const float* coord, const int64_t* segment, const int32_t* order, const int32_t* idx_ptr, int64_t K,
+                      const int64_t* h_vacancy, int num_vacancy, float* bbox, float* centroid, ss_stream_t stream);
+int ss_instance_scatter(const int32_t* cluster, int64_t n, int64_t K, const float* centroid, void* instance, int instance_is_i64,
+                        int64_t ignore_index, float* instance_centroid, ss_stream_t stream);
 /* GridSample(apply_to_pc=True) over the point cloud beside the Gaussians (transform.py:1245-1253).  order / idx_ptr: the CSR that
  * ss_pool_partition wrote over a stable argsort of the cell keys (cell c holds rows order[idx_ptr[c] .. idx_ptr[c+1]), ascending).
  * chosen[c] = the first of them whose label (int64, indexed by row) differs from ignore_index; the first member when the cell has

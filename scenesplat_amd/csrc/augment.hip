@@ -3,6 +3,9 @@
 // Four HBM-bound one-pass kernels, fp32, in place; the host (pointcept_api/transform.py) draws the random parameters, composes
 // the rigid ops into ONE affine + quaternion + reflection and hands them over as kernel arguments, so nothing but the per-point
 // arrays is read from memory.  One thread per point, grid-stride, at most AUG_MAX_BLOCKS workgroups.
+// Behind them the kernels of the transforms outside the shipped lists (transform.py:423-434, 1035-1100, 1620-1664): the fp64 HSV round
+// trip of HueSaturationTranslation, the fp64 moments NormalizeCoord folds into the pending affine, and InstanceParser's per-instance
+// boxes and centroids over a sorted CSR (one workgroup per instance).  No float atomics: every result is the same on every run.
 #include "common.h"
 #include <math.h>
 
@@ -245,6 +248,184 @@ k_voxel_pick_labelled(const int32_t* __restrict__ order, const int32_t* __restri
   }
 }
 
+// ---- HueSaturationTranslation ---------------------------------------------------------------------------------------------------
+// transform.py:1037-1100 per point, in fp64 and in the reference's operation order: it truncates twice through uint8 (the sector
+// i = (h * 6.0).astype("uint8") and the final rgb.astype("uint8")), so a value that an fp32 evaluation or a fused multiply-add
+// moves across an integer changes the output by a whole step.  No contraction in here; the divisions are IEEE.
+__device__ __forceinline__ double np_mod1(double a) {          // numpy's a % 1.0: fmod, lifted by 1 when negative (may give exactly 1.0)
+#pragma clang fp contract(off)
+  double r = fmod(a, 1.0);
+  if (r < 0.0) r += 1.0;
+  return r;
+}
+
+__device__ __forceinline__ float to_u8(double v) {             // astype("uint8") on 0..255; outside it (numpy: undefined) saturates, NaN -> 0
+  return v >= 255.0 ? 255.0f : (v >= 0.0 ? (float)(int)v : 0.0f);
+}
+
+__global__ void __launch_bounds__(AUG_BLOCK)
+k_aug_hsv(float* __restrict__ color, int64_t n, double hue_val, double sat_ratio) {
+#pragma clang fp contract(off)
+  for (int64_t i = (int64_t)blockIdx.x * AUG_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * AUG_BLOCK) {
+    const double r = color[3 * i], g = color[3 * i + 1], b = color[3 * i + 2];
+    const double maxc = fmax(r, fmax(g, b)), minc = fmin(r, fmin(g, b));
+    const double v = maxc;
+    double s = 0.0, rc = 0.0, gc = 0.0, bc = 0.0;
+    if (maxc != minc) {
+      const double d = maxc - minc;
+      s = d / maxc;
+      rc = (maxc - r) / d; gc = (maxc - g) / d; bc = (maxc - b) / d;
+    }
+    double h = r == maxc ? bc - gc : (g == maxc ? (2.0 + rc) - bc : (4.0 + gc) - rc);
+    h = np_mod1(h / 6.0);
+    h = np_mod1((hue_val + h) + 1.0);
+    s = fmin(fmax(sat_ratio * s, 0.0), 1.0);
+    const double h6 = h * 6.0;
+    const int sector = (int)to_u8(h6);
+    const double f = h6 - (double)sector;
+    const double p = v * (1.0 - s);
+    const double q = v * (1.0 - s * f);
+    const double t = v * (1.0 - s * (1.0 - f));
+    double o0 = v, o1 = t, o2 = p;                               // sector 0 (and 6: h == 1.0)
+    if (s == 0.0) { o0 = v; o1 = v; o2 = v; }
+    else switch (sector % 6) {
+      case 1: o0 = q; o1 = v; o2 = p; break;
+      case 2: o0 = p; o1 = v; o2 = t; break;
+      case 3: o0 = p; o1 = q; o2 = v; break;
+      case 4: o0 = t; o1 = p; o2 = v; break;
+      case 5: o0 = v; o1 = p; o2 = q; break;
+      default: break;
+    }
+    color[3 * i] = to_u8(o0); color[3 * i + 1] = to_u8(o1); color[3 * i + 2] = to_u8(o2);
+  }
+}
+
+// ---- fp64 moments of A x + b ----------------------------------------------------------------------------------------------------
+// NormalizeCoord's two reductions: the sums of the three components (the centroid) and the largest squared norm.  fp64, the
+// products and sums uncontracted in the written order, so the maximum is the value numpy gives for the same expression.  Per-block
+// partials and a one-wave finish: a fixed tree, the same bits on every run.
+struct Affine64 { double a[9]; double b[3]; };
+
+__device__ __forceinline__ double wave_reduce_sum64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_reduce_max64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+__global__ void __launch_bounds__(AUG_BLOCK)
+k_aug_moments(const float* __restrict__ x, int64_t n, Affine64 af, int use_affine, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+  __shared__ double red[AUG_WAVES][4];
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int64_t i = (int64_t)blockIdx.x * AUG_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * AUG_BLOCK) {
+    const double px = x[3 * i], py = x[3 * i + 1], pz = x[3 * i + 2];
+    double p[3] = {px, py, pz};
+    if (use_affine) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) p[j] = ((af.a[3 * j] * px + af.a[3 * j + 1] * py) + af.a[3 * j + 2] * pz) + af.b[j];
+    }
+    acc[0] += p[0]; acc[1] += p[1]; acc[2] += p[2];
+    acc[3] = fmax(acc[3], (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]);
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double r = j < 3 ? wave_reduce_sum64(acc[j]) : wave_reduce_max64(acc[j]);
+    if (lane == 0) red[wave][j] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double r = red[0][threadIdx.x];
+    for (int w = 1; w < AUG_WAVES; ++w) r = threadIdx.x < 3 ? r + red[w][threadIdx.x] : fmax(r, red[w][threadIdx.x]);
+    partials[(int64_t)blockIdx.x * 4 + threadIdx.x] = r;
+  }
+}
+
+__global__ void __launch_bounds__(64)
+k_aug_moments_finish(const double* __restrict__ partials, int nb, double* __restrict__ out4) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double r = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 64) r = j < 3 ? r + partials[b * 4 + j] : fmax(r, partials[b * 4 + j]);
+    r = j < 3 ? wave_reduce_sum64(r) : wave_reduce_max64(r);
+    if (threadIdx.x == 0) out4[j] = r;
+  }
+}
+
+// ---- InstanceParser -------------------------------------------------------------------------------------------------------------
+// transform.py:1626-1664 over the CSR of a stable argsort of the instance ids (instance k holds rows order[idx_ptr[k] .. idx_ptr[k+1]),
+// ascending).  One workgroup per instance, the whole workgroup striding the run (one instance may hold almost every row): min / max
+// are exact, the coordinate sum is fp64 in a fixed order (thread-strided, wave tree, waves in order) and is rounded to fp32 once.
+constexpr int INST_MAX_VACANCY = 16;
+struct Vacancy { int64_t v[INST_MAX_VACANCY]; int count; };
+
+__global__ void __launch_bounds__(AUG_BLOCK)
+k_instance_boxes(const float* __restrict__ coord, const int64_t* __restrict__ segment, const int32_t* __restrict__ order,
+                 const int32_t* __restrict__ idx_ptr, int64_t K, Vacancy vac, float* __restrict__ bbox, float* __restrict__ centroid) {
+#pragma clang fp contract(off)
+  __shared__ float red_lo[AUG_WAVES][3], red_hi[AUG_WAVES][3];
+  __shared__ double red_sum[AUG_WAVES][3];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int64_t k = blockIdx.x; k < K; k += gridDim.x) {
+    const int32_t lo_j = idx_ptr[k], hi_j = idx_ptr[k + 1];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    double sum[3] = {0.0, 0.0, 0.0};
+    for (int32_t j = lo_j + (int32_t)threadIdx.x; j < hi_j; j += AUG_BLOCK) {
+      const int64_t r = order[j];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float p = coord[3 * r + c];
+        lo[c] = fminf(lo[c], p); hi[c] = fmaxf(hi[c], p); sum[c] += (double)p;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float l = wave_reduce_min(lo[c]), h = wave_reduce_max(hi[c]);
+      const double s = wave_reduce_sum64(sum[c]);
+      if (lane == 0) { red_lo[wave][c] = l; red_hi[wave][c] = h; red_sum[wave][c] = s; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+      const int c = threadIdx.x;
+      float l = red_lo[0][c], h = red_hi[0][c];
+      double s = red_sum[0][c];
+      for (int w = 1; w < AUG_WAVES; ++w) { l = fminf(l, red_lo[w][c]); h = fmaxf(h, red_hi[w][c]); s += red_sum[w][c]; }
+      bbox[8 * k + c] = (h + l) / 2.0f;
+      bbox[8 * k + 3 + c] = h - l;
+      centroid[3 * k + c] = (float)(s / (double)(hi_j - lo_j));
+    }
+    if (threadIdx.x == 3) {
+      const int64_t cls = segment[order[lo_j]];                 // the run's first member: segment[mask_][0] (the sort is stable)
+      int below = 0;
+      for (int v = 0; v < vac.count; ++v) below += cls > vac.v[v] ? 1 : 0;
+      bbox[8 * k + 6] = 0.0f;
+      bbox[8 * k + 7] = (float)cls - (float)below;
+    }
+    __syncthreads();
+  }
+}
+
+// cluster[row] = the run of the row; runs K and above (the ignored rows' sentinel run) get the ignore value in both outputs
+__global__ void __launch_bounds__(AUG_BLOCK)
+k_instance_scatter(const int32_t* __restrict__ cluster, int64_t n, int64_t K, const float* __restrict__ centroid, void* __restrict__ instance,
+                   int is64, int64_t ignore_index, float* __restrict__ out) {
+  const float ign = (float)ignore_index;
+  for (int64_t i = (int64_t)blockIdx.x * AUG_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * AUG_BLOCK) {
+    const int64_t k = cluster ? cluster[i] : K;
+    const bool member = k >= 0 && k < K;
+    const int64_t id = member ? k : ignore_index;
+    if (is64) static_cast<int64_t*>(instance)[i] = id; else static_cast<int32_t*>(instance)[i] = (int32_t)id;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3 * i + c] = member ? centroid[3 * k + c] : ign;
+  }
+}
+
 }  // namespace
 
 extern "C" int ss_aug_bbox_blocks(int64_t n) { return aug_blocks(n); }
@@ -311,6 +492,52 @@ extern "C" int ss_aug_color(float* color, int64_t n, int flags, const float* h_l
   P.flags = flags; P.normalize = normalize ? 1 : 0; P.blend = blend; P.jitter_scale = jitter_std * 255.0f; P.seed = seed;
   SS_LAUNCH(k_aug_color, dim3((unsigned)aug_blocks(n)), dim3(AUG_BLOCK), 0, stream, color, n, P,
             (flags & 4) ? noise : (const float*)nullptr);
+  return SS_OK;
+}
+
+extern "C" int ss_aug_hsv(float* color, int64_t n, const double* h_hue_sat, hipStream_t stream) {
+  if (n < 0 || !h_hue_sat) return SS_ERR_ARG;
+  if (n == 0) return SS_OK;
+  if (!color) return SS_ERR_ARG;
+  SS_LAUNCH(k_aug_hsv, dim3((unsigned)aug_blocks(n)), dim3(AUG_BLOCK), 0, stream, color, n, h_hue_sat[0], h_hue_sat[1]);
+  return SS_OK;
+}
+
+extern "C" int ss_aug_moments_blocks(int64_t n) { return aug_blocks(n); }
+
+extern "C" int ss_aug_moments(const float* x, int64_t n, const double* h_affine, double* partials, double* out4, hipStream_t stream) {
+  if (n < 1 || !x || !partials || !out4) return SS_ERR_ARG;
+  Affine64 af = {};
+  if (h_affine) {
+    for (int i = 0; i < 9; ++i) af.a[i] = h_affine[i];
+    for (int i = 0; i < 3; ++i) af.b[i] = h_affine[9 + i];
+  }
+  const int nb = aug_blocks(n);
+  SS_LAUNCH(k_aug_moments, dim3((unsigned)nb), dim3(AUG_BLOCK), 0, stream, x, n, af, h_affine ? 1 : 0, partials);
+  SS_LAUNCH(k_aug_moments_finish, dim3(1), dim3(64), 0, stream, (const double*)partials, nb, out4);
+  return SS_OK;
+}
+
+extern "C" int ss_instance_boxes(const float* coord, const int64_t* segment, const int32_t* order, const int32_t* idx_ptr, int64_t K,
+                                 const int64_t* h_vacancy, int num_vacancy, float* bbox, float* centroid, hipStream_t stream) {
+  if (K < 0 || num_vacancy < 0 || num_vacancy > INST_MAX_VACANCY || (num_vacancy && !h_vacancy)) return SS_ERR_ARG;
+  if (K == 0) return SS_OK;
+  if (!coord || !segment || !order || !idx_ptr || !bbox || !centroid) return SS_ERR_ARG;
+  Vacancy vac = {};
+  for (int i = 0; i < num_vacancy; ++i) vac.v[i] = h_vacancy[i];
+  vac.count = num_vacancy;
+  const unsigned grid = (unsigned)(K > AUG_MAX_BLOCKS ? AUG_MAX_BLOCKS : K);
+  SS_LAUNCH(k_instance_boxes, dim3(grid), dim3(AUG_BLOCK), 0, stream, coord, segment, order, idx_ptr, K, vac, bbox, centroid);
+  return SS_OK;
+}
+
+extern "C" int ss_instance_scatter(const int32_t* cluster, int64_t n, int64_t K, const float* centroid, void* instance, int instance_is_i64,
+                                   int64_t ignore_index, float* instance_centroid, hipStream_t stream) {
+  if (n < 0 || K < 0) return SS_ERR_ARG;
+  if (n == 0) return SS_OK;
+  if (!instance || !instance_centroid || (K > 0 && (!cluster || !centroid))) return SS_ERR_ARG;
+  SS_LAUNCH(k_instance_scatter, dim3((unsigned)aug_blocks(n)), dim3(AUG_BLOCK), 0, stream, K > 0 ? cluster : (const int32_t*)nullptr, n, K,
+            centroid, instance, instance_is_i64 ? 1 : 0, ignore_index, instance_centroid);
   return SS_OK;
 }
 

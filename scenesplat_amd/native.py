@@ -1023,6 +1023,69 @@ def aug_color_(color, flags=0, lo=None, hi=None, blend=0.0, tr=None, jitter_std=
                              _stream()), "ss_aug_color")
 
 
+def _hd(values, count, name):
+    """A few host doubles that travel as kernel arguments -> ctypes double array (None stays NULL)."""
+    if values is None:
+        return None
+    v = [float(x) for x in values]
+    if len(v) != count:
+        raise RuntimeError(f"{name}: expected {count} values, got {len(v)}")
+    return (ctypes.c_double * count)(*v)
+
+
+def aug_hsv_(color, hue_val, sat_ratio):
+    """HueSaturationTranslation's pass on color (n, 3), 0..255, in place: the reference's fp64 HSV round trip, truncated to integers."""
+    _rows3(color, "color")
+    check(lib().ss_aug_hsv(_p(color), color.shape[0], _hd((hue_val, sat_ratio), 2, "hue_sat"), _stream()), "ss_aug_hsv")
+    return color
+
+
+def aug_moments(x, affine=None):
+    """(4,) f64 device tensor {sum x, sum y, sum z, max squared norm} of x (n, 3) f32, or of A x + b for affine = 12 host doubles."""
+    _rows3(x, "x")
+    n = x.shape[0]
+    if n < 1:
+        raise RuntimeError("aug_moments: empty input")
+    part = torch.empty((lib().ss_aug_moments_blocks(n), 4), dtype=torch.float64, device=x.device)
+    out = torch.empty(4, dtype=torch.float64, device=x.device)
+    check(lib().ss_aug_moments(_p(x), n, _hd(affine, 12, "affine"), _p(part), _p(out), _stream()), "ss_aug_moments")
+    return out
+
+
+INSTANCE_MAX_VACANCY = 16
+
+
+def instance_boxes(coord, segment, order, idx_ptr, K, vacancy=()):
+    """-> bbox (K, 8) f32, centroid (K, 3) f32 of the K leading runs of the CSR (order, idx_ptr); see include/scenesplat_hip.h."""
+    _rows3(coord, "coord")
+    n, K = coord.shape[0], int(K)
+    _req(segment, torch.int64, "segment", (n,)); _req(order, torch.int32, "order"); _req(idx_ptr, torch.int32, "idx_ptr")
+    if K < 0 or (K > 0 and (idx_ptr.numel() < K + 1 or order.numel() > n)):
+        raise RuntimeError("instance_boxes: idx_ptr shorter than K + 1, or order longer than coord")
+    vac = [int(v) for v in vacancy]
+    if len(vac) > INSTANCE_MAX_VACANCY:
+        raise RuntimeError(f"instance_boxes: at most {INSTANCE_MAX_VACANCY} non-negative ignore indices, got {len(vac)}")
+    bbox = torch.empty((K, 8), dtype=torch.float32, device=coord.device)
+    centroid = torch.empty((K, 3), dtype=torch.float32, device=coord.device)
+    check(lib().ss_instance_boxes(_p(coord), _p(segment), _p(order), _p(idx_ptr), K, (ctypes.c_int64 * len(vac))(*vac) if vac else None,
+                                  len(vac), _p(bbox), _p(centroid), _stream()), "ss_instance_boxes")
+    return bbox, centroid
+
+
+def instance_scatter_(instance, cluster, K, centroid, ignore_index):
+    """instance (n,) int32 / int64 <- dense id per row, in place; -> instance_centroid (n, 3) f32.  Rows of a run >= K: ignore_index."""
+    _req(instance, None, "instance")
+    if instance.dim() != 1 or instance.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"instance: expected (n,) int32 / int64, got {tuple(instance.shape)} {instance.dtype}")
+    n, K = instance.shape[0], int(K)
+    if K > 0:
+        _req(cluster, torch.int32, "cluster", (n,)); _req(centroid, torch.float32, "centroid", (K, 3))
+    out = torch.empty((n, 3), dtype=torch.float32, device=instance.device)
+    check(lib().ss_instance_scatter(_p(cluster) if K > 0 else None, n, K, _p(centroid) if K > 0 else None, _p(instance),
+                                    int(instance.dtype == torch.int64), int(ignore_index), _p(out), _stream()), "ss_instance_scatter")
+    return out
+
+
 # ---- the SSL view generator's colour chain and sparse voxel blur (csrc/ssl_views.hip) --------
 CHAIN_BRIGHTNESS, CHAIN_CONTRAST, CHAIN_SATURATION, CHAIN_HUE, CHAIN_GRAY = 1, 2, 3, 4, 5
 CHAIN_MAX_STEPS = 8

@@ -13,6 +13,8 @@ from . import transform  # noqa: F401  (registers the per-sample training transf
 from .transform import Compose  # noqa: F401
 from .transform import (CollectContrast, ContrastiveViewsGenerator_SSL, GSGaussianBlurVoxelOpc, RandomColorGrayScale,  # noqa: F401
                         RandomColorJitter, RandomColorSolarize, SphereCropRandomMaxPoints)   # (the self-supervised view generator)
+from .transform import (Add, ContrastiveViewsGenerator, CropBoundary, HueSaturationTranslation, InstanceParser,  # noqa: F401
+                        NormalizeCoord, PointClip, PositiveShift, RandomColorDrop, ShufflePoint)   # (the rest of the reference's transforms)
 from . import ppt  # noqa: F401  (registers PPT-v1m2)
 from .pdnorm import PDNorm  # noqa: F401  (registered in MODULES)
 from . import tester  # noqa: F401  (registers ZeroShotSemSegTester)

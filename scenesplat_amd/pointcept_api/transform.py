@@ -22,6 +22,12 @@ Two things differ from the reference by design:
 rotations, RandomScale and RandomFlip move the cloud with the Gaussians (a second pending affine, one more ``ss_aug_gaussians`` launch
 per flush), ``GridSample(apply_to_pc=True)`` keeps one point per occupied cell of the cloud's own grid, every other op passes both keys through.
 
+The alternatives the shipped lists carry commented out, and the rest of the reference's per-sample transforms, are here too:
+NormalizeCoord and PositiveShift fold into the pending affine (``RigidState.moments`` is to NormalizeCoord what ``bbox`` is to
+CenterShift: an fp64 reduction of the pending ``A x + b``, a 4-double readback), HueSaturationTranslation is one ``ss_aug_hsv`` pass
+(the reference's fp64 HSV round trip, bit for bit), InstanceParser two kernels over a sorted CSR of the instance ids; RandomColorDrop,
+PointClip, ShufflePoint, CropBoundary, Add and ContrastiveViewsGenerator need no kernel of their own.
+
 All ops work IN PLACE on float32 contiguous tensors (as the reference mutates its arrays) and refuse CPU tensors: there is no
 CPU fallback.  ``draw``, the host composition (``RigidState`` with a ``bbox_fn``) and ``box_blur3`` need no device.
 """
@@ -129,8 +135,9 @@ class RigidState:
     RandomShift and RandomJitter do not, so the two affines differ after them.  The flush rules are shared."""
     family = "rigid"
 
-    def __init__(self, bbox_fn=None):
+    def __init__(self, bbox_fn=None, moments_fn=None):
         self.bbox_fn = bbox_fn
+        self.moments_fn = moments_fn      # (A, b) -> {mean xyz, largest squared norm}: the host stand-in of moments(), as bbox_fn is of bbox()
         self.reset()
 
     def reset(self):
@@ -161,6 +168,18 @@ class RigidState:
         if self.bbox_fn is not None:
             return np.asarray(self.bbox_fn(self.A, self.b), dtype=np.float64)
         return nv.aug_bbox(_dev(data["coord"], "coord", 3), self.affine12()).cpu().numpy().astype(np.float64)
+
+    def moments(self, data):
+        """{mean xyz, largest squared norm} of the current coordinates in fp64, pending affine included (ss_aug_moments: a 4-double
+        readback)."""
+        if self.jitter is not None:
+            self.flush(data)
+        if self.moments_fn is not None:
+            return np.asarray(self.moments_fn(self.A, self.b), dtype=np.float64)
+        coord = _dev(data["coord"], "coord", 3)
+        m = nv.aug_moments(coord, self.affine12()).cpu().numpy()
+        m[:3] /= coord.shape[0]
+        return m
 
     def before_coord_op(self, data):
         if self.jitter is not None:           # the kernel adds the jitter last
@@ -933,6 +952,242 @@ class CollectContrast(Transform):
             assert isinstance(keys, (list, tuple))
             data[name.replace("_keys", "")] = torch.cat([data_dict[k].float() for k in keys], dim=1)
         return data
+
+
+# ---- the alternatives the shipped lists carry commented out, and the rest of the reference's per-sample transforms ---------------
+@TRANSFORMS.register_module()
+class HueSaturationTranslation(Transform):
+    """transform.py:1035-1100: hue shifted by hue_val = (u - 0.5) 2 hue_max, saturation scaled by 1 + (u' - 0.5) 2 saturation_max,
+    through the reference's fp64 HSV round trip that truncates to whole colour values (ss_aug_hsv: one pass, in place).  No family:
+    a pending colour pass is flushed first, so the op sees what the chromatic ops in front of it wrote."""
+
+    def __init__(self, hue_max=0.5, saturation_max=0.2):
+        self.hue_max, self.saturation_max = hue_max, saturation_max
+
+    def draw(self, rng, data_dict):
+        return dict(hue_val=float((rng.random() - 0.5) * 2 * self.hue_max),
+                    sat_ratio=float(1 + (rng.random() - 0.5) * 2 * self.saturation_max))
+
+    def apply(self, data_dict, params):
+        if "color" in data_dict:
+            nv.aug_hsv_(_dev(data_dict["color"], "color", 3), params["hue_val"], params["sat_ratio"])
+        return data_dict
+
+
+@TRANSFORMS.register_module()
+class RandomColorDrop(Transform):
+    """transform.py:1103-1117: with probability p, color *= color_augment."""
+
+    def __init__(self, p=0.2, color_augment=0.0):
+        self.p, self.color_augment = p, color_augment
+
+    def draw(self, rng, data_dict):
+        return dict(fired=bool(rng.random() < self.p))
+
+    def apply(self, data_dict, params):
+        if params["fired"] and "color" in data_dict:
+            _dev(data_dict["color"], "color").mul_(self.color_augment)
+        return data_dict
+
+    def __repr__(self):
+        return "RandomColorDrop(color_augment: {}, p: {})".format(self.color_augment, self.p)
+
+
+@TRANSFORMS.register_module()
+class NormalizeCoord(Transform):
+    """transform.py:423-434: coord <- (coord - centroid) / m, m = the largest distance from the centroid, and scale <- scale / m.
+    Folds into the pending affine: ss_aug_moments of the pending A x + b gives the centroid, a second call after the shift the
+    largest squared norm (a 4-double readback each, fp64), and the division rides the run's ss_aug_gaussians pass.  pc_coord stays
+    as it is, as in the reference."""
+    family = "rigid"
+
+    def fold(self, state, data_dict, params):
+        if "coord" in data_dict:
+            state.shift(data_dict, -state.moments(data_dict)[:3])
+            m2 = float(state.moments(data_dict)[3])
+            if not m2 > 0.0:                                  # the reference divides by m = 0 here and fills coord with NaN
+                raise ValueError("NormalizeCoord: every point lies on the centroid")
+            state.scale(data_dict, 1.0 / np.sqrt(m2))
+
+
+@TRANSFORMS.register_module()
+class PositiveShift(Transform):
+    """transform.py:437-443: coord -= its per-axis minimum (the bounding box of the pending affine); pc_coord stays as it is."""
+    family = "rigid"
+
+    def fold(self, state, data_dict, params):
+        if "coord" in data_dict:
+            state.shift(data_dict, -state.bbox(data_dict)[:3])
+
+
+@TRANSFORMS.register_module()
+class PointClip(Transform):
+    """transform.py:482-494: coord clipped to point_cloud_range = (x0, y0, z0, x1, y1, z1)."""
+
+    def __init__(self, point_cloud_range=(-80, -80, -3, 80, 80, 1)):
+        self.point_cloud_range = point_cloud_range
+
+    def apply(self, data_dict, params):
+        if "coord" in data_dict:
+            coord = _dev(data_dict["coord"], "coord", 3)
+            coord.clamp_(coord.new_tensor([float(v) for v in self.point_cloud_range[:3]]),
+                         coord.new_tensor([float(v) for v in self.point_cloud_range[3:]]))
+        return data_dict
+
+
+@TRANSFORMS.register_module()
+class Add(Transform):
+    """transform.py:402-412: data_dict[key] = value for every entry of keys_dict (host only)."""
+
+    def __init__(self, keys_dict=None):
+        self.keys_dict = dict() if keys_dict is None else keys_dict
+
+    def apply(self, data_dict, params):
+        for key, value in self.keys_dict.items():
+            data_dict[key] = value
+        return data_dict
+
+
+def _row_keys(*extra):
+    return DROPOUT_KEYS + tuple(k for k in extra if k not in DROPOUT_KEYS)
+
+
+# The reference permutes coord / grid_coord / displacement / color / normal / segment / instance and masks the same without
+# displacement: on a Gaussian sample that leaves quat / scale / opacity / lang_feat paired with other rows.  Every per-point key moves here.
+SHUFFLE_KEYS = _row_keys("grid_coord", "displacement")
+CROP_BOUNDARY_KEYS = _row_keys("grid_coord")
+
+
+def _take_keys(data_dict, keys, idx):
+    idx32 = idx.to(torch.int32).contiguous()
+    for k in keys:
+        v = data_dict.get(k)
+        if isinstance(v, torch.Tensor):
+            data_dict[k] = gt.take_rows(v, idx32)
+    return data_dict
+
+
+@TRANSFORMS.register_module()
+class ShufflePoint(Transform):
+    """transform.py:1551-1571: the rows in a random order (torch.randperm on a seeded device generator, as RandomDropout draws);
+    params["idx"] replays a recorded permutation.  Moves SHUFFLE_KEYS."""
+
+    def draw(self, rng, data_dict):
+        return dict(seed=_seed(rng))
+
+    def apply(self, data_dict, params):
+        assert "coord" in data_dict
+        coord = data_dict["coord"]
+        if not isinstance(coord, torch.Tensor) or not coord.is_cuda:
+            raise RuntimeError("ShufflePoint: GPU tensors required (no CPU fallback)")
+        n = coord.shape[0]
+        if params.get("idx") is not None:
+            idx = torch.as_tensor(np.asarray(params["idx"]), dtype=torch.int64).to(coord.device)
+            if idx.shape != (n,):
+                raise ValueError(f"ShufflePoint: a recorded permutation of {tuple(idx.shape)} for {n} rows")
+        else:
+            g = torch.Generator(device=coord.device)
+            g.manual_seed(int(params["seed"]))
+            idx = torch.randperm(n, device=coord.device, generator=g)
+        return _take_keys(data_dict, SHUFFLE_KEYS, idx)
+
+
+@TRANSFORMS.register_module()
+class CropBoundary(Transform):
+    """transform.py:1574-1592: the rows whose segment is neither 0 nor 1, in order.  Moves CROP_BOUNDARY_KEYS."""
+
+    def apply(self, data_dict, params):
+        assert "segment" in data_dict
+        segment = data_dict["segment"]
+        if not isinstance(segment, torch.Tensor) or not segment.is_cuda:
+            raise RuntimeError("CropBoundary: GPU tensors required (no CPU fallback)")
+        segment = segment.reshape(-1)
+        return _take_keys(data_dict, CROP_BOUNDARY_KEYS, torch.nonzero((segment != 0) & (segment != 1)).reshape(-1))
+
+
+@TRANSFORMS.register_module()
+class ContrastiveViewsGenerator(Transform):
+    """transform.py:1595-1617: two clones of `view_keys`, view_trans_cfg (a Compose of this module: it fuses like its parent) run
+    on each -> view1_<key> / view2_<key> for every key a view ends with.  Both runs draw from the caller's Generator, one after
+    the other, as the reference's two runs share the global stream: draw() hands it over; params["views"] = [params list of run
+    1, of run 2] replays a recorded call instead."""
+
+    def __init__(self, view_keys=("coord", "color", "normal", "origin_coord"), view_trans_cfg=None):
+        self.view_keys = view_keys
+        self.view_trans = Compose(view_trans_cfg)
+
+    def set_fuse(self, fuse):
+        self.view_trans.set_fuse(fuse)
+
+    def draw(self, rng, data_dict):
+        return dict(rng=rng)
+
+    def _clone(self, d):
+        return {k: (d[k].clone() if isinstance(d[k], torch.Tensor) else copy.deepcopy(d[k])) for k in self.view_keys}
+
+    def apply(self, data_dict, params):
+        views = params.get("views")
+        if views is not None and len(views) != 2:
+            raise ValueError(f"ContrastiveViewsGenerator: 2 params lists expected, got {len(views)}")
+        view1, view2 = self._clone(data_dict), self._clone(data_dict)
+        view1 = self.view_trans(view1, params=None if views is None else views[0], rng=params.get("rng"))
+        view2 = self.view_trans(view2, params=None if views is None else views[1], rng=params.get("rng"))
+        for key, value in view1.items():
+            data_dict["view1_" + key] = value
+        for key, value in view2.items():
+            data_dict["view2_" + key] = value
+        return data_dict
+
+
+@TRANSFORMS.register_module()
+class InstanceParser(Transform):
+    """transform.py:1620-1664: rows whose segment is in segment_ignore_index get instance_ignore_index; the ids of the others
+    become dense (0 .. K-1 in ascending order of the raw id -- signed: an id of -1 on a valid segment is an instance of its own,
+    as np.unique makes it); `instance` is rewritten in place, `instance_centroid` (n, 3) holds each row's instance centroid and
+    `bbox` (K, 8) = {centre, size, 0, class} with the class index shifted down past the non-negative ignore indices.  Both are
+    fp32 (the reference: fp64 arrays of fp32 values).  The ids are ordered by the stable radix argsort with the ignored rows keyed
+    past every id, ss_pool_partition turns the order into the CSR, ss_instance_boxes / ss_instance_scatter do the rest; two small
+    readbacks (the id range, K)."""
+
+    def __init__(self, segment_ignore_index=(-1, 0, 1), instance_ignore_index=-1):
+        self.segment_ignore_index = segment_ignore_index
+        self.instance_ignore_index = instance_ignore_index
+
+    def apply(self, data_dict, params):
+        coord = _dev(data_dict["coord"], "coord", 3)
+        segment, instance = data_dict["segment"], data_dict["instance"]
+        for t, name in ((segment, "segment"), (instance, "instance")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError(f"{name}: scenesplat_amd transforms need a GPU tensor (no CPU fallback)")
+        n = coord.shape[0]
+        if instance.shape != (n,) or instance.dtype not in (torch.int32, torch.int64) or not instance.is_contiguous():
+            raise RuntimeError(f"instance: must be a contiguous (n,) int32 / int64 tensor (it is updated in place), got "
+                               f"{tuple(instance.shape)} {instance.dtype}")
+        segment = segment.reshape(-1).to(torch.int64).contiguous()
+        if segment.shape[0] != n:
+            raise RuntimeError(f"segment: {segment.shape[0]} rows, coord has {n}")
+        ignore = [int(v) for v in self.segment_ignore_index]
+        K, cluster, order, idx_ptr = 0, None, None, None
+        if n > 0:
+            valid = ~torch.isin(segment, torch.tensor(ignore, dtype=torch.int64, device=coord.device)) if ignore else \
+                torch.ones(n, dtype=torch.bool, device=coord.device)
+            ids = instance.to(torch.int64)
+            big = torch.iinfo(torch.int64).max
+            lo, hi, count = torch.stack([torch.where(valid, ids, big).min(), torch.where(valid, ids, -big).max(), valid.sum()]).tolist()
+            if count > 0:
+                span = hi - lo
+                if span >= (1 << 62):
+                    raise ValueError("InstanceParser: instance ids span more than 2^62")
+                key = torch.where(valid, ids - lo, span + 1).contiguous()
+                order, _, _ = nv.argsort_i64(key[None], (span + 1).bit_length(), want_inverse=False, want_sorted=False)
+                order = order[0]
+                cluster, idx_ptr, _, n_out = nv.pool_partition(key, order, 0)
+                K = int(n_out.item()) - (1 if count < n else 0)
+        bbox, centroid = nv.instance_boxes(coord, segment, order, idx_ptr, K, [v for v in ignore if v >= 0]) if K > 0 else \
+            (torch.empty((0, 8), dtype=torch.float32, device=coord.device), None)
+        data_dict["instance_centroid"] = nv.instance_scatter_(instance, cluster, K, centroid, self.instance_ignore_index)
+        data_dict["bbox"] = bbox
+        return data_dict
 
 
 class Compose:
