@@ -926,6 +926,36 @@ int ss_pca_project(const void* x, int dtype, int64_t N, int D, const float* shif
                    float* extremes, void* workspace, size_t workspace_bytes, ss_stream_t stream);
 int ss_pca_colors(const float* y, const float* extremes, int64_t N, int k, float* colors, ss_stream_t stream);
 
+/* ---- text queries on scene features (csrc/text_query.hip; the definition: DESIGN.md 8t) ------------------------------------------
+ * x (N, D) on the device as for the PCA entries (any D and alignment; wide loads when D % 4 == 0 and x is aligned to them), 1 <= N <
+ * 2^31, 1 <= D <= SS_QUERY_MAX_DIM.  t_hat (Q, D) f32 on the device: the UNIT text embeddings (the caller normalises them in fp64),
+ * 1 <= Q <= SS_QUERY_MAX_QUERIES.  valid (N) bytes on the device or NULL.  Anything outside the limits: SS_ERR_ARG; a workspace below
+ * the size its *_workspace_bytes function names: SS_ERR_WORKSPACE.  No float atomics anywhere: two runs agree bit for bit.
+ * ss_query_scores: scores (Q, N) f32, query-major: (sum_d x[r][d] * t_hat[q][d]) / max(sqrt(sum_d x[r][d]^2), 1e-12) in fp32, the sums
+ *   as fmaf chains in a fixed order (v_mfma_f32_32x32x2_f32 for the products).  A row with valid[r] == 0, a zero norm or a score that
+ *   is not finite is DEAD: -inf for every query.  -0.0 is written as +0.0.  stats (Q, 3) f64 = {live rows, sum s, sum s^2} over the
+ *   live rows, from the fp32 scores.  A workgroup takes rows in blocks of SS_QUERY_ROWS; its fp64 partials are added in index order.
+ * ss_query_select: scores (Q, N) as written above.  h_tau (Q) f32 and h_m (Q) int32 are HOST arrays (they travel as kernel arguments).
+ *   The candidates of query q are the live rows (s > -inf) with s >= h_tau[q] (-inf: every live row).  h_m[q] < 0: all C of them are
+ *   selected; else the min(h_m[q], C) best: descending score, the lower row first among equal scores, -0.0 equal to +0.0 (an exact
+ *   radix select on the fp32 scores; rows are shared out in segments of SS_QUERY_SELECT_ROWS).  bitmap (Q, ss_pc_bitmap_words(N))
+ *   uint32, every word written: what ss_pc_compact_scan / ss_pc_compact (nc = Q) turn into ascending rows.  counts (Q) int32: the
+ *   selected rows.  tau_out (Q) f32: h_tau[q], but the score of the last row kept when the cap binds (h_m[q] < C) or when h_m[q] >= 0
+ *   and h_tau[q] == -inf (+inf when nothing is kept).
+ * ss_query_best: best (N) int32 = among the queries whose bitmap holds row r the one of highest score (the lowest q among equals), -1
+ *   when none does. */
+#define SS_QUERY_MAX_DIM 1024
+#define SS_QUERY_MAX_QUERIES 32
+#define SS_QUERY_ROWS 256
+#define SS_QUERY_SELECT_ROWS 2048
+size_t ss_query_scores_workspace_bytes(int64_t N, int Q);
+int ss_query_scores(const void* x, int dtype, int64_t N, int D, const float* t_hat, int Q, const uint8_t* valid, float* scores,
+                    double* stats, void* workspace, size_t workspace_bytes, ss_stream_t stream);
+size_t ss_query_select_workspace_bytes(int64_t N, int Q);
+int ss_query_select(const float* scores, int64_t N, int Q, const float* h_tau, const int32_t* h_m, uint32_t* bitmap, float* tau_out,
+                    int32_t* counts, void* workspace, size_t workspace_bytes, ss_stream_t stream);
+int ss_query_best(const float* scores, const uint32_t* bitmap, int64_t N, int Q, int32_t* best, ss_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2274,3 +2274,70 @@ def pca_colors(y, extremes):
     colors = torch.empty((y.shape[0], 3), dtype=torch.float32, device=y.device)
     check(lib().ss_pca_colors(_p(y), _p(extremes), y.shape[0], y.shape[1], _p(colors), _stream()), "ss_pca_colors")
     return colors
+
+
+# ---- text queries on scene features (csrc/text_query.hip) ------------------------------------------------------------
+QUERY_MAX_DIM, QUERY_MAX_QUERIES = _C["SS_QUERY_MAX_DIM"], _C["SS_QUERY_MAX_QUERIES"]
+QUERY_ROWS, QUERY_SELECT_ROWS = _C["SS_QUERY_ROWS"], _C["SS_QUERY_SELECT_ROWS"]
+
+
+def query_scores_workspace_bytes(N, Q):
+    return int(lib().ss_query_scores_workspace_bytes(N, Q))
+
+
+def query_scores(x, t_hat, valid=None, workspace=None):
+    """ss_query_scores: x (N, D) f32 / f16 / bf16, t_hat (Q, D) f32 unit rows, valid (N,) uint8 / bool or None -> (scores (Q, N) f32:
+    cosine scores, -inf in dead rows; stats (Q, 3) f64 = {live rows, sum s, sum s^2}); workspace: a uint8 tensor of
+    query_scores_workspace_bytes(N, Q) bytes (None: allocated here)"""
+    _req(x, None, "features"); _req(t_hat, torch.float32, "t_hat")
+    if x.dim() != 2 or x.dtype not in _PCA_DTYPES or x.shape[0] < 1 or not 1 <= x.shape[1] <= QUERY_MAX_DIM:
+        raise RuntimeError(f"features: expected (N >= 1, 1 <= D <= {QUERY_MAX_DIM}) float32 / float16 / bfloat16, got "
+                           f"{tuple(x.shape)} {x.dtype}")
+    N, D = x.shape
+    if t_hat.dim() != 2 or t_hat.shape[1] != D or not 1 <= t_hat.shape[0] <= QUERY_MAX_QUERIES:
+        raise RuntimeError(f"t_hat: expected (1 <= Q <= {QUERY_MAX_QUERIES}, {D}), got {tuple(t_hat.shape)}")
+    Q = t_hat.shape[0]
+    if valid is not None:
+        _req(valid, None, "valid", (N,))
+        if valid.dtype not in (torch.uint8, torch.bool):
+            raise RuntimeError(f"valid: expected uint8 or bool, got {valid.dtype}")
+    scores = torch.empty((Q, N), dtype=torch.float32, device=x.device)
+    stats = torch.empty((Q, 3), dtype=torch.float64, device=x.device)
+    ws = _pca_ws(workspace, query_scores_workspace_bytes(N, Q), x.device)
+    check(lib().ss_query_scores(_p(x), _PCA_DTYPES[x.dtype], N, D, _p(t_hat), Q, _p(valid), _p(scores), _p(stats), _p(ws), ws.numel(),
+                                _stream()), "ss_query_scores")
+    return scores, stats
+
+
+def query_select_workspace_bytes(N, Q):
+    return int(lib().ss_query_select_workspace_bytes(N, Q))
+
+
+def query_select(scores, tau, m, workspace=None):
+    """ss_query_select: scores (Q, N) f32 as query_scores writes them; tau: Q host floats (rounded to fp32; -inf: no threshold); m: Q
+    host ints (negative: no cap) -> (bitmap (Q, ceil(N / 32)) int32 words, tau_out (Q,) f32, counts (Q,) int32)"""
+    _req(scores, torch.float32, "scores")
+    if scores.dim() != 2 or scores.shape[1] < 1 or not 1 <= scores.shape[0] <= QUERY_MAX_QUERIES:
+        raise RuntimeError(f"scores: expected (1 <= Q <= {QUERY_MAX_QUERIES}, N >= 1), got {tuple(scores.shape)}")
+    Q, N = scores.shape
+    tau = np.ascontiguousarray(np.asarray(tau, dtype=np.float32).reshape(-1))
+    m = np.ascontiguousarray(np.clip(np.asarray(m, dtype=np.int64).reshape(-1), -1, 2 ** 31 - 1).astype(np.int32))
+    if tau.shape[0] != Q or m.shape[0] != Q:
+        raise RuntimeError(f"query_select: expected {Q} thresholds and caps, got {tau.shape[0]} and {m.shape[0]}")
+    bitmap = torch.empty((Q, lib().ss_pc_bitmap_words(N)), dtype=torch.int32, device=scores.device)
+    tau_out = torch.empty(Q, dtype=torch.float32, device=scores.device)
+    counts = torch.empty(Q, dtype=torch.int32, device=scores.device)
+    ws = _pca_ws(workspace, query_select_workspace_bytes(N, Q), scores.device)
+    check(lib().ss_query_select(_p(scores), N, Q, tau.ctypes.data, m.ctypes.data, _p(bitmap), _p(tau_out), _p(counts), _p(ws), ws.numel(),
+                                _stream()), "ss_query_select")
+    return bitmap, tau_out, counts
+
+
+def query_best(scores, bitmap):
+    """ss_query_best: -> best (N,) int32: the selecting query of highest score per row (the lowest q among equals), -1 when none"""
+    _req(scores, torch.float32, "scores")
+    Q, N = scores.shape
+    _req(bitmap, torch.int32, "bitmap", (Q, lib().ss_pc_bitmap_words(N)))
+    best = torch.empty(N, dtype=torch.int32, device=scores.device)
+    check(lib().ss_query_best(_p(scores), _p(bitmap), N, Q, _p(best), _stream()), "ss_query_best")
+    return best

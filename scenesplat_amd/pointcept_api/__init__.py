@@ -68,4 +68,9 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".feature_pca", __name__)
         return module if name == "feature_pca" else getattr(module, name)
+    # text_query (text queries on saved features: scores, exact selection, the selected Gaussians as a scene folder), and its command line
+    if name in ("text_query", "query_scene", "load_text_queries", "extract_geometry", "highlight_colors"):
+        import importlib
+        module = importlib.import_module(".text_query", __name__)
+        return module if name == "text_query" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
