@@ -33,6 +33,8 @@
  *   ss_knn_query ... ss_bfs_cluster           libs/pointops/src/pointops_api.cpp:15-31,
  *                                             libs/pointops2/src/pointops_api.cpp:17-44,
  *                                             libs/pointgroup_ops/src/bfs_cluster.cpp:140-145
+ *   ss_splat_project ... ss_splat_composite   tools/visualize_scene.py:57-201 (the Open3D point cloud / ellipsoid meshes and the
+ *                                             matplotlib scatter; docs/ROADMAP.md task 3), as a headless splat rasteriser
  */
 #ifndef SCENESPLAT_HIP_H
 #define SCENESPLAT_HIP_H
@@ -955,6 +957,52 @@ size_t ss_query_select_workspace_bytes(int64_t N, int Q);
 int ss_query_select(const float* scores, int64_t N, int Q, const float* h_tau, const int32_t* h_m, uint32_t* bitmap, float* tau_out,
                     int32_t* counts, void* workspace, size_t workspace_bytes, ss_stream_t stream);
 int ss_query_best(const float* scores, const uint32_t* bitmap, int64_t N, int Q, int32_t* best, ss_stream_t stream);
+
+/* ---- headless Gaussian-splat rendering (csrc/splat.hip; the definition is DESIGN.md 8u) -----------------------------------------------
+ * A scene's rows -- coord (N, 3), scale (N, 3) (exponentiated), quat (N, 4) = w, x, y, z, opacity (N), color (N, 3) in 0..1, all f32 on
+ * the device -- become an image by EWA splatting: project, count the (Gaussian, tile) pairs, sort them by (tile, depth) with
+ * ss_argsort_i64, composite front to back.  Forward only.  No atomics of any kind: two runs give the same bits.  Every buffer is the
+ * caller's.  Limits (anything else: SS_ERR_ARG): 1 <= N < 2^31, 1 <= width, height <= SS_SPLAT_MAX_DIM, 1 <= P < 2^31.
+ * Preconditions the kernels do not check: ss_splat_keys, ss_splat_ranges and ss_splat_composite take rect / tiles_touched / depth as
+ *   ss_splat_project wrote them for the same camera, offsets and P as ss_splat_offsets wrote them for those tiles_touched, and keys /
+ *   order / ranges / sorted_rows as the step before wrote them (ss_splat_keys alone guards its writes against P).
+ * h_camera: a HOST block of SS_SPLAT_CAMERA_WORDS 32-bit words (it travels as a kernel argument): f32 R[9] (world to camera, row
+ *   major), t[3], fx, fy, cx, cy, near, limx, limy (1.3 tan(fov / 2) per axis), then int32 width, height, then zeros.  The camera looks
+ *   down +z, x right, y down; pixel (i, j) has its centre at (i + 0.5, j + 0.5); tiles are SS_SPLAT_TILE square.
+ * ss_splat_project: per row mean2d (N, 2) f32, conic_opacity (N, 4) f32 = {conic xx, xy, yy, opacity}, depth (N) f32 = p_c.z,
+ *   rect (N, 4) int32 = {x0, y0, x1, y1} in tiles (x1, y1 exclusive), radius (N) int32 or NULL, tiles_touched (N) int32 = the
+ *   rectangle's area; all 0 for a culled row (a non-finite input, |q| == 0, p_c.z <= near, det <= 0 or NaN, a derived value that is
+ *   not finite, an empty rectangle).  mode SS_SPLAT_MODE_POINTCLOUD: the 2-D covariance is (point_size / 3)^2 I and the opacity 1.
+ * ss_splat_offsets: offsets (N) int64 = the exclusive running sum of tiles_touched; totals (2) int64 = {P, rows with tiles_touched
+ *   > 0}.  Two levels over blocks of SS_SPLAT_SCAN_ROWS rows; workspace ss_splat_offsets_workspace_bytes(N), else SS_ERR_WORKSPACE.
+ * ss_splat_keys: keys (P) int64 = (tile << 32) | bits(depth) with tile = y * tiles_x + x, rows (P) int32 = the pair's row, at
+ *   offsets[row] + the tile's rank in the rectangle (y major).  Sort them with ss_argsort_i64 (key_bits = 32 + ceil(log2(tiles))).
+ * ss_splat_ranges: sorted_keys / order = what the sort wrote.  ranges (num_tiles, 2) int32 = [start, end) of each tile in the sorted
+ *   pairs ({0, 0} for a tile without any), sorted_rows (P) int32 = rows[order[i]].
+ * ss_splat_composite: one workgroup per tile, one pixel per lane, the tile's Gaussians staged SS_SPLAT_BATCH at a time.  Per pixel,
+ *   from T = 1: power = -0.5 d^T conic d (> 0 skips), alpha = min(0.99, o exp(power)) (< 1/255 skips), T' = T (1 - alpha) (< 1e-4
+ *   stops the pixel before adding), else C += c alpha T, Z += depth alpha T, T = T'.  image (H, W, 3) = C + T background, alpha (H, W)
+ *   = 1 - T, depth_out (H, W) = Z.  h_background: 3 HOST floats. */
+#define SS_SPLAT_TILE 16
+#define SS_SPLAT_BATCH 256
+#define SS_SPLAT_MAX_DIM 4096
+#define SS_SPLAT_CAMERA_WORDS 24
+#define SS_SPLAT_SCAN_ROWS 2048
+#define SS_SPLAT_MODE_GAUSSIANS 0
+#define SS_SPLAT_MODE_POINTCLOUD 1
+int ss_splat_project(const float* coord, const float* scale, const float* quat, const float* opacity, const float* color, int64_t N,
+                     const void* h_camera, int mode, float scale_modifier, float point_size, float* mean2d, float* conic_opacity,
+                     float* depth, int32_t* rect, int32_t* radius, int32_t* tiles_touched, ss_stream_t stream);
+size_t ss_splat_offsets_workspace_bytes(int64_t N);
+int ss_splat_offsets(const int32_t* tiles_touched, int64_t N, int64_t* offsets, int64_t* totals, void* workspace,
+                     size_t workspace_bytes, ss_stream_t stream);
+int ss_splat_keys(const float* depth, const int32_t* rect, const int32_t* tiles_touched, const int64_t* offsets, int64_t N, int64_t P,
+                  int tiles_x, int tiles_y, int64_t* keys, int32_t* rows, ss_stream_t stream);
+int ss_splat_ranges(const int64_t* sorted_keys, const int32_t* order, const int32_t* rows, int64_t P, int num_tiles, int32_t* ranges,
+                    int32_t* sorted_rows, ss_stream_t stream);
+int ss_splat_composite(const float* mean2d, const float* conic_opacity, const float* color, const float* depth, const int32_t* ranges,
+                       const int32_t* sorted_rows, int64_t N, int64_t P, int width, int height, const float* h_background, float* image,
+                       float* alpha, float* depth_out, ss_stream_t stream);
 
 #ifdef __cplusplus
 }

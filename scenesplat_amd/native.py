@@ -2341,3 +2341,114 @@ def query_best(scores, bitmap):
     best = torch.empty(N, dtype=torch.int32, device=scores.device)
     check(lib().ss_query_best(_p(scores), _p(bitmap), N, Q, _p(best), _stream()), "ss_query_best")
     return best
+
+
+# ---- headless Gaussian-splat rendering (csrc/splat.hip) ---------------------------------------------------------------
+SPLAT_TILE, SPLAT_BATCH, SPLAT_MAX_DIM = _C["SS_SPLAT_TILE"], _C["SS_SPLAT_BATCH"], _C["SS_SPLAT_MAX_DIM"]
+SPLAT_CAMERA_WORDS, SPLAT_SCAN_ROWS = _C["SS_SPLAT_CAMERA_WORDS"], _C["SS_SPLAT_SCAN_ROWS"]
+SPLAT_MODES = {"gaussians": _C["SS_SPLAT_MODE_GAUSSIANS"], "pointcloud": _C["SS_SPLAT_MODE_POINTCLOUD"]}
+SPLAT_MAX_PAIRS = 2 ** 31 - 1          # the largest count ss_argsort_i64 takes
+
+
+def _splat_camera(camera):
+    """the packed camera block: SPLAT_CAMERA_WORDS 32-bit words in a contiguous host array -> (block, width, height)"""
+    cam = np.ascontiguousarray(camera)
+    if cam.dtype.itemsize != 4 or cam.size != SPLAT_CAMERA_WORDS:
+        raise RuntimeError(f"camera: expected a packed block of {SPLAT_CAMERA_WORDS} 32-bit words, got {cam.dtype} x {cam.size}")
+    w, h = (int(v) for v in cam.reshape(-1).view(np.int32)[19:21])
+    if not (1 <= w <= SPLAT_MAX_DIM and 1 <= h <= SPLAT_MAX_DIM):
+        raise RuntimeError(f"camera: width and height must be in 1..{SPLAT_MAX_DIM}, got {w} x {h}")
+    return cam, w, h
+
+
+def splat_project(coord, scale, quat, opacity, color, camera, mode="gaussians", scale_modifier=1.0, point_size=2.0):
+    """ss_splat_project: coord (N, 3), scale (N, 3), quat (N, 4), opacity (N,), color (N, 3), all f32; camera: the packed host block ->
+    dict(mean2d (N, 2) f32, conic_opacity (N, 4) f32, depth (N,) f32, rect (N, 4) int32, radius (N,) int32, tiles_touched (N,) int32)"""
+    _req(coord, torch.float32, "coord")
+    if coord.dim() != 2 or coord.shape[1] != 3 or coord.shape[0] < 1:
+        raise RuntimeError(f"coord: expected (N >= 1, 3), got {tuple(coord.shape)}")
+    N, dev = coord.shape[0], coord.device
+    _req(scale, torch.float32, "scale", (N, 3)); _req(quat, torch.float32, "quat", (N, 4))
+    _req(opacity, torch.float32, "opacity", (N,)); _req(color, torch.float32, "color", (N, 3))
+    if mode not in SPLAT_MODES:
+        raise RuntimeError(f"mode must be one of {tuple(SPLAT_MODES)}, got {mode!r}")
+    cam, _, _ = _splat_camera(camera)
+    out = dict(mean2d=torch.empty((N, 2), dtype=torch.float32, device=dev), conic_opacity=torch.empty((N, 4), dtype=torch.float32, device=dev),
+               depth=torch.empty(N, dtype=torch.float32, device=dev), rect=torch.empty((N, 4), dtype=torch.int32, device=dev),
+               radius=torch.empty(N, dtype=torch.int32, device=dev), tiles_touched=torch.empty(N, dtype=torch.int32, device=dev))
+    check(lib().ss_splat_project(_p(coord), _p(scale), _p(quat), _p(opacity), _p(color), N, cam.ctypes.data, SPLAT_MODES[mode],
+                                 float(scale_modifier), float(point_size), _p(out["mean2d"]), _p(out["conic_opacity"]), _p(out["depth"]),
+                                 _p(out["rect"]), _p(out["radius"]), _p(out["tiles_touched"]), _stream()), "ss_splat_project")
+    return out
+
+
+def splat_offsets_workspace_bytes(N):
+    return int(lib().ss_splat_offsets_workspace_bytes(N))
+
+
+def splat_offsets(tiles_touched, workspace=None):
+    """ss_splat_offsets: tiles_touched (N,) int32 -> (offsets (N,) int64: its exclusive running sum, totals (2,) int64 = {P, visible rows});
+    workspace: a uint8 tensor of splat_offsets_workspace_bytes(N) bytes (None: allocated here)"""
+    _req(tiles_touched, torch.int32, "tiles_touched")
+    if tiles_touched.dim() != 1 or tiles_touched.shape[0] < 1:
+        raise RuntimeError(f"tiles_touched: expected (N >= 1,), got {tuple(tiles_touched.shape)}")
+    N, dev = tiles_touched.shape[0], tiles_touched.device
+    offsets = torch.empty(N, dtype=torch.int64, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = _ws(splat_offsets_workspace_bytes(N), dev) if workspace is None else _req(workspace, torch.uint8, "workspace")
+    check(lib().ss_splat_offsets(_p(tiles_touched), N, _p(offsets), _p(totals), _p(ws), ws.numel(), _stream()), "ss_splat_offsets")
+    return offsets, totals
+
+
+def splat_keys(depth, rect, tiles_touched, offsets, P, tiles_x, tiles_y):
+    """ss_splat_keys: -> (keys (P,) int64 = (tile << 32) | bits(depth), rows (P,) int32)"""
+    _req(depth, torch.float32, "depth")
+    N, dev = depth.shape[0], depth.device
+    _req(rect, torch.int32, "rect", (N, 4)); _req(tiles_touched, torch.int32, "tiles_touched", (N,))
+    _req(offsets, torch.int64, "offsets", (N,))
+    P = int(P)
+    keys = torch.empty(P, dtype=torch.int64, device=dev)
+    rows = torch.empty(P, dtype=torch.int32, device=dev)
+    check(lib().ss_splat_keys(_p(depth), _p(rect), _p(tiles_touched), _p(offsets), N, P, int(tiles_x), int(tiles_y), _p(keys), _p(rows),
+                              _stream()), "ss_splat_keys")
+    return keys, rows
+
+
+def splat_ranges(sorted_keys, order, rows, num_tiles):
+    """ss_splat_ranges: sorted_keys (P,) int64 and order (P,) int32 as argsort_i64 wrote them, rows (P,) int32 -> (ranges (num_tiles, 2)
+    int32, sorted_rows (P,) int32 = rows[order])"""
+    _req(sorted_keys, torch.int64, "sorted_keys")
+    P, dev = sorted_keys.numel(), sorted_keys.device
+    _req(order, torch.int32, "order"); _req(rows, torch.int32, "rows", (P,))
+    if order.numel() != P:
+        raise RuntimeError(f"order: expected {P} entries, got {order.numel()}")
+    ranges = torch.empty((int(num_tiles), 2), dtype=torch.int32, device=dev)
+    sorted_rows = torch.empty(P, dtype=torch.int32, device=dev)
+    check(lib().ss_splat_ranges(_p(sorted_keys), _p(order), _p(rows), P, int(num_tiles), _p(ranges), _p(sorted_rows), _stream()),
+          "ss_splat_ranges")
+    return ranges, sorted_rows
+
+
+def splat_composite(mean2d, conic_opacity, color, depth, ranges, sorted_rows, width, height, background, out=None):
+    """ss_splat_composite: -> (image (H, W, 3) f32, alpha (H, W) f32, depth (H, W) f32); background: 3 host floats; out: the three
+    tensors to write (None: allocated here)"""
+    _req(mean2d, torch.float32, "mean2d")
+    N, dev = mean2d.shape[0], mean2d.device
+    _req(mean2d, torch.float32, "mean2d", (N, 2)); _req(conic_opacity, torch.float32, "conic_opacity", (N, 4))
+    _req(color, torch.float32, "color", (N, 3)); _req(depth, torch.float32, "depth", (N,))
+    width, height = int(width), int(height)
+    tiles = _div_up(width, SPLAT_TILE) * _div_up(height, SPLAT_TILE)
+    _req(ranges, torch.int32, "ranges", (tiles, 2)); _req(sorted_rows, torch.int32, "sorted_rows")
+    P = sorted_rows.numel()
+    bg = np.ascontiguousarray(np.asarray(background, dtype=np.float32).reshape(-1))
+    if bg.shape[0] != 3:
+        raise RuntimeError(f"background: expected 3 values, got {bg.shape[0]}")
+    if out is None:
+        out = (torch.empty((height, width, 3), dtype=torch.float32, device=dev), torch.empty((height, width), dtype=torch.float32, device=dev),
+               torch.empty((height, width), dtype=torch.float32, device=dev))
+    image, alpha, zmap = out
+    _req(image, torch.float32, "image", (height, width, 3)); _req(alpha, torch.float32, "alpha", (height, width))
+    _req(zmap, torch.float32, "depth image", (height, width))
+    check(lib().ss_splat_composite(_p(mean2d), _p(conic_opacity), _p(color), _p(depth), _p(ranges), _p(sorted_rows), N, P, width, height,
+                                   bg.ctypes.data, _p(image), _p(alpha), _p(zmap), _stream()), "ss_splat_composite")
+    return image, alpha, zmap

@@ -73,4 +73,9 @@ def __getattr__(name):
         import importlib
         module = importlib.import_module(".text_query", __name__)
         return module if name == "text_query" else getattr(module, name)
+    # render (a scene folder as alpha-composited Gaussian splats: an image tensor and a PNG, no viewer), and its command line
+    if name in ("render", "render_scene", "look_at_camera", "fit_camera", "orbit_cameras", "save_image", "Camera"):
+        import importlib
+        module = importlib.import_module(".render", __name__)
+        return module if name == "render" else getattr(module, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
